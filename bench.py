@@ -15,15 +15,22 @@ One "step" = one full-batch Adam step of every member (featurise, forward,
 likelihood + prior, backward, Adam) - reference inference.py:599-607.  The whole
 K-step loop is enqueued by ONE C call (bnf_train) with inputs resident in HBM.
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline      dominant kernel: algorithmic FLOPs per launch / its mean HIP-event
-                duration inside the timed region, vs the dense bf16 MFMA peak.
-  cpu_baseline  the oracle's algorithm on torch CPU float32 with torch.bmm over members (a port of
-                the reference algorithm, NOT JAX) timed on this box's host cores on a bounded
-                sample (N=1 only).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up,
+device preheat, W warm-up steps, the K timed steps, the line.  Extra objects:
   device_preheat  ms of untimed steps on a SCRATCH engine before the W warm-up steps of the measured one
                 (--preheat-ms, default 100, 0 = off): after an idle period the device ramps for ~8 steps
                 whatever engine runs on it (profiles/r03_device_ramp.txt); a fit is thousands of steps.
+With --full also:
+  roofline      dominant kernel: algorithmic FLOPs per launch / its mean HIP-event
+                duration inside the timed region, vs the dense bf16 MFMA peak.
+  other_dtypes  the same step under the engine's other arithmetics, short runs (N=1 only).
+  cpu_baseline  the oracle's algorithm on torch CPU float32 with torch.bmm over members (a port of
+                the reference algorithm, NOT JAX) timed on this box's host cores on a bounded
+                sample (N=1 only; --no-cpu-baseline skips it and other_dtypes).
+--dump-outputs DIR writes what the timed call (Engine.train) hands back for its last step, rank 0's
+members: loss.npy, float32 (members,).  The inputs are fixed seeds, so two builds run with the same
+arguments can be compared file for file, to fp32 rounding: the engine sums row-panel contributions
+with float atomics, whose order varies from run to run.
 `--gpus N` without a launcher starts the N ranks itself (torch.distributed.run, 127.0.0.1) and
 refuses to run when fewer than N devices are visible; the line carries `rccl_world_size` (from an
 actual all_reduce), every rank's ms/step and, for N > 1, the one posterior all-gather.
@@ -487,10 +494,22 @@ def gather_posterior_inproc(parts, lib=None):
   return out, (time.perf_counter() - t0) * 1e3, 'peer-copies', err
 
 
+def timed_outputs(losses):
+  """--dump-outputs: what the timed call returns for its last step -> {name: float32 array}.
+  losses (members, K), the tensor Engine.train hands back: its last column."""
+  return {'loss': losses[:, -1].float().cpu().numpy()}
+
+
+def dump_outputs(out_dir, outputs):
+  os.makedirs(out_dir, exist_ok=True)
+  for name, arr in outputs.items():
+    np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def run_rank(args, rank, device, E, data, sync):
   """One rank's share of the job (one process per GPU, or one host thread per GPU under --launcher inproc):
   engine set-up, device preheat, W warm-up steps, then EXACTLY K timed steps between two `sync()` rendezvous.
-  -> dict(elapsed, prof, dominant, final_loss, net, eng, local_means | None)."""
+  -> dict(elapsed, prof, dominant, final_loss, net, eng, local_means | None, outputs | None)."""
   import torch
   X, y, input_scales = data
   if args.selftest_cpu:
@@ -504,8 +523,11 @@ def run_rank(args, rank, device, E, data, sync):
     t0 = time.perf_counter()
     run_steps(args.steps)
     sync()
-    return dict(elapsed=time.perf_counter() - t0, prof=None, dominant='selftest', final_loss=0.0, net=None, eng=None,
-                local_means=torch.full((E, 16), float(rank), device=device), device=str(device))
+    elapsed = time.perf_counter() - t0
+    means = torch.full((E, 16), float(rank), device=device)
+    outputs = timed_outputs(torch.full((E, args.steps), float(rank))) if args.dump_outputs else None
+    return dict(elapsed=elapsed, prof=None, dominant='selftest', final_loss=0.0, net=None, eng=None,
+                local_means=means, device=str(device), outputs=outputs)
   from bayesnf_amd.engine import Engine
   from bayesnf_amd.spec import NetSpec
   net = NetSpec(input_scales=input_scales, **MODEL_KW)
@@ -525,33 +547,40 @@ def run_rank(args, rank, device, E, data, sync):
       torch.cuda.synchronize(device)
       ep_h += 8
     scratch.close()
-  # ---- warm-up (also finds the dominant kernel) --------------------------------
-  eng.profile('*')
+  # ---- warm-up (--full / --profile-all: with HIP events on every kernel, to find the dominant one) ----
+  profiled = args.full or args.profile_all
+  if profiled:
+    eng.profile('*')
   eng.train(0, max(args.warmup, 1))
   sync()
-  warm = eng.profile_read()
-  eng.profile(None)
-  total_ms = {k: v['avg_ms'] * v['calls'] for k, v in warm.items()}
-  dominant = max(total_ms, key=total_ms.get)
-  if args.profile_all and rank == 0:
-    for k, v in sorted(warm.items(), key=lambda kv: -total_ms[kv[0]]):
-      tf = v['flops'] / (v['avg_ms'] * 1e-3) / 1e12 if v['flops'] else 0.0
-      print(f'[bench] {k:16s} avg {v["avg_ms"]*1e3:9.1f} us  x{v["calls"]:4d}  '
-            f'{tf:8.1f} TFLOP/s', file=sys.stderr)
-  # ---- timed region: exactly K steps, events only around the dominant kernel ---
-  eng.profile(dominant)
+  prof = dominant = None
+  if profiled:
+    warm = eng.profile_read()
+    eng.profile(None)
+    total_ms = {k: v['avg_ms'] * v['calls'] for k, v in warm.items()}
+    dominant = max(total_ms, key=total_ms.get)
+    if args.profile_all and rank == 0:
+      for k, v in sorted(warm.items(), key=lambda kv: -total_ms[kv[0]]):
+        tf = v['flops'] / (v['avg_ms'] * 1e-3) / 1e12 if v['flops'] else 0.0
+        print(f'[bench] {k:16s} avg {v["avg_ms"]*1e3:9.1f} us  x{v["calls"]:4d}  '
+              f'{tf:8.1f} TFLOP/s', file=sys.stderr)
+  # ---- timed region: exactly K steps (--full: events around the dominant kernel for the roofline) ----
+  if args.full:
+    eng.profile(dominant)
   sync()
   t0 = time.perf_counter()
   losses = eng.train(args.warmup, args.steps)
   sync()
   elapsed = time.perf_counter() - t0
-  prof = eng.profile_read()
-  eng.profile(None)
+  if args.full:
+    prof = eng.profile_read()
+    eng.profile(None)
   final_loss = float(losses[:, -1].mean().item())
   if not np.isfinite(final_loss):
     raise RuntimeError('non-finite training loss in the benchmark run')
+  outputs = timed_outputs(losses) if args.dump_outputs else None
   return dict(elapsed=elapsed, prof=prof, dominant=dominant, final_loss=final_loss, net=net, eng=eng, local_means=None,
-              device=str(device))
+              device=str(device), outputs=outputs)
 
 
 def side_dtype_lines(args, device, E, X, y, input_scales, flops_step):
@@ -620,7 +649,14 @@ def main(argv=None):
   ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32', 'fp32_split', 'fp8'],
                   help="bf16 (the headline), fp32 (the parity arithmetic), fp8 = bf16 contractions with fp8 operand storage for "
                        'the weight-gradient streams (BASELINE configs[4])')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline does not need: the roofline of the dominant kernel (HIP events '
+                       'in the warm-up and the timed region) and, for N = 1, the other arithmetics and the CPU baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help="after the timed steps, write rank 0's outputs of the last step to DIR as float32 .npy files "
+                       '(loss.npy; see the module docstring)')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='with --full: skip the other arithmetics and the CPU baseline')
   ap.add_argument('--preheat-ms', type=float, default=100.0,
                   help='bring the DEVICE to the power / clock state a long fit runs in: this many ms of untimed steps on a '
                        'scratch engine (other parameters, other buffers) before the W warm-up steps of the measured engine; '
@@ -797,28 +833,31 @@ def main(argv=None):
     }
     if gather is not None:
       line['posterior_gather'] = gather
+    if args.dump_outputs:
+      dump_outputs(args.dump_outputs, r0['outputs'])
     if args.selftest_cpu:
       line['selftest'] = True
     else:
       prof, dominant, net = r0['prof'], r0['dominant'], r0['net']
       line['device_preheat'] = {'ms': args.preheat_ms, 'what': 'untimed steps of a scratch engine (other parameters and buffers) '
                                 'before the W warm-up steps of the measured engine: device power / clock state; --preheat-ms 0 = off'}
-      d = prof[dominant]
-      achieved = d['flops'] / (d['avg_ms'] * 1e-3) / 1e12 if d['flops'] else 0.0
-      peak = PEAK_TFLOPS[args.dtype]
       flops_step = net.flops_per_member_step(len(y)) * total_members
       line['algorithmic_tflops'] = flops_step * args.steps / elapsed / 1e12
-      traffic, traffic_src = pmc_traffic(dominant, args.dtype, E)
-      ctr, ctr_src = sq_counters(dominant, args.dtype, E)
-      line['roofline'] = {'bound': 'mfma', 'kernel': dominant, 'achieved': achieved, 'peak': peak,
-                          'unit': 'TFLOP/s', 'frac': achieved / peak,
-                          'traffic': traffic, 'traffic_source': traffic_src,
-                          'avg_launch_us': d['avg_ms'] * 1e3, 'launches': d['calls'],
-                          'flops_per_launch': d['flops'],
-                          'issue_floors': issue_floors(ctr, d['avg_ms'] * 1e3), 'issue_floors_source': ctr_src}
-      if world == 1 and not args.no_cpu_baseline:
-        line['other_dtypes'] = side_dtype_lines(args, device, E, X, y, input_scales, flops_step)
-        line['cpu_baseline'] = cpu_baseline(X, y, input_scales)
+      if args.full:
+        d = prof[dominant]
+        achieved = d['flops'] / (d['avg_ms'] * 1e-3) / 1e12 if d['flops'] else 0.0
+        peak = PEAK_TFLOPS[args.dtype]
+        traffic, traffic_src = pmc_traffic(dominant, args.dtype, E)
+        ctr, ctr_src = sq_counters(dominant, args.dtype, E)
+        line['roofline'] = {'bound': 'mfma', 'kernel': dominant, 'achieved': achieved, 'peak': peak,
+                            'unit': 'TFLOP/s', 'frac': achieved / peak,
+                            'traffic': traffic, 'traffic_source': traffic_src,
+                            'avg_launch_us': d['avg_ms'] * 1e3, 'launches': d['calls'],
+                            'flops_per_launch': d['flops'],
+                            'issue_floors': issue_floors(ctr, d['avg_ms'] * 1e3), 'issue_floors_source': ctr_src}
+        if world == 1 and not args.no_cpu_baseline:
+          line['other_dtypes'] = side_dtype_lines(args, device, E, X, y, input_scales, flops_step)
+          line['cpu_baseline'] = cpu_baseline(X, y, input_scales)
     print(json.dumps(line), flush=True)
   for r in results:
     if r['eng'] is not None:

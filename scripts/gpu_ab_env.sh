@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_panel.py tests/test_gpu_parity.py te
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
   for rep in 1 2; do
-    env $envs timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
+    env $envs timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
     python -c "import json;d=json.load(open('$OUT/bench_$name.json'));print('$name ms/step',round(d['ms_per_step'],4),'value',round(d['value']),'panel us',round(d['roofline']['avg_launch_us'],1),'frac',round(d['roofline']['frac'],4))"
   done
 done

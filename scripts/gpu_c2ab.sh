@@ -7,7 +7,7 @@ first=${1%%:*}
 for rep in 1 2 3; do
   for spec in "$@"; do
     v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*:}
-    env $envs BNF_LIB=$ROOT/ab/libbnf_$v.so timeout 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    env $envs BNF_LIB=$ROOT/ab/libbnf_$v.so timeout 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$spec', 'ms/step', round(d['ms_per_step'],4), 'panel_us', round(d['roofline']['avg_launch_us'],1), 'frac', round(d['roofline']['frac'],4))"
   done

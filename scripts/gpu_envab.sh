@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=$1; KEXPR=$2; shift 2; OUT=$ROOT/gpurun_out
 for rep in 1 2 3; do
   for spec in "$@"; do
     v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*:}
-    env $envs timeout 200 python bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
+    env $envs timeout 200 python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$v', 'ms/step', round(d['ms_per_step'],4), 'panel_us', round(d['roofline']['avg_launch_us'],1), 'frac', round(d['roofline']['frac'],4))"
   done

@@ -13,7 +13,7 @@ echo "== diag";   timeout 900 python tests/gpu_diag.py > "$OUT/diag.txt" 2>&1; e
 echo "== pytest"; timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider > "$OUT/pytest.txt" 2>&1; echo "pytest rc=$?"
 tail -5 "$OUT/pytest.txt"
 echo "== smoke";  timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1; echo "smoke rc=$?"
-echo "== bench";  timeout 900 python bench.py --steps 20 --warmup 3 --profile-all > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+echo "== bench";  timeout 900 python bench.py --full --steps 20 --warmup 3 --profile-all > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 cat "$OUT/bench.json"; tail -20 "$OUT/bench.err"
 echo "== rocprof"
 cd /tmp && export TMPDIR=/tmp

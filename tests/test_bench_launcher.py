@@ -64,6 +64,51 @@ def test_single_rank_line_has_the_contract_fields():
   assert d['n_gpus'] == 1 and d['rccl_world_size'] == 1 and 'posterior_gather' not in d
 
 
+def test_dump_outputs_writes_rank0_last_step_as_float32(tmp_path):
+  """`--dump-outputs DIR`: after the timed steps, loss.npy (members,) in float32 -- the last column of what the timed
+  call returns, here the stand-in step's (rank 0's); `--steps` is the number of timed steps the line reports."""
+  out = tmp_path / 'out'
+  r = _run(['--selftest-cpu', '--gpus', '2', '--steps', '3', '--warmup', '1', '--members-per-gpu', '4',
+            '--dump-outputs', str(out)])
+  assert r.returncode == 0, r.stderr[-2000:]
+  d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+  assert d['steps'] == 3 and abs(d['value'] - 8 * 3 / (d['ms_per_step'] * 3e-3)) < 1e-6 * d['value']
+  import numpy as np
+  assert sorted(p.name for p in out.iterdir()) == ['loss.npy']
+  loss = np.load(out / 'loss.npy')
+  assert loss.dtype == np.float32 and loss.shape == (4,) and np.all(loss == 0.0)     # rank 0's members
+
+
+def test_timed_outputs_are_the_last_step_of_the_returned_losses():
+  import numpy as np
+  import torch
+  import bench
+  losses = torch.arange(15, dtype=torch.float32).reshape(3, 5)
+  out = bench.timed_outputs(losses)
+  assert list(out) == ['loss'] and out['loss'].dtype == np.float32
+  np.testing.assert_array_equal(out['loss'], [4.0, 9.0, 14.0])
+
+
+def test_bench_inputs_are_the_same_every_run():
+  import numpy as np
+  import bench
+  (Xa, ya, sa), (Xb, yb, sb) = bench.synthetic_grid(), bench.synthetic_grid()
+  assert Xa.shape == (10232, 3)
+  np.testing.assert_array_equal(Xa, Xb)
+  np.testing.assert_array_equal(ya, yb)
+  np.testing.assert_array_equal(sa, sb)
+
+
+def test_plain_and_full_runs_parse_and_keep_the_contract_fields():
+  for extra in ([], ['--full']):
+    r = _run(['--selftest-cpu', '--steps', '2', '--warmup', '1'] + extra)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+      assert key in d
+    assert d['steps'] == 2 and d['unit'] == 'member-steps/s' and d['higher_is_better'] is True
+
+
 def test_more_gpus_than_visible_fails_loudly():
   r = _run(['--gpus', '2', '--steps', '1', '--warmup', '1'])
   assert r.returncode != 0
