@@ -142,8 +142,6 @@ struct bnf_handle {
   int32_t* leaf_off = nullptr; uint8_t* leaf_id = nullptr; int32_t n_leaves = 0;
   bool adam_clear_all = false;   // env BNF_ADAM_CLEAR_ALL (A/B of the kept gradient range)
   bool h0l = false;
-  bool fin = false;     // -DBNF_PANEL_FIN=1 builds + env BNF_PANEL_FIN=1: the H0L panel forms featurise their own rows (measured loss)
-  int32_t* fcol = nullptr; std::vector<int32_t> fcol_h;   // per padded feature column {kind | group << 8, a, b, 0}
   bool fold0 = false;   // the panel kernel's F0 forms: layer-0 scale / bias folded into its contraction (needs h0l, F + 2 <= Fp)
   void* A[BNF_MAX_LAYERS]; void* H[BNF_MAX_LAYERS]; void* Ht[BNF_MAX_LAYERS];
   void* dZ[BNF_MAX_LAYERS]; void* dZt[BNF_MAX_LAYERS];
@@ -190,6 +188,12 @@ struct bnf_handle {
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
+// the H0L panel forms (feature panel staged in LDS) exist for these shapes
+static bool panel_h0l(const bnf_handle* h) {
+  const bool shape = ((h->W == 512 || h->W == 1024) && h->Fp == 64) || (h->W == 256 && (h->Fp == 64 || h->Fp == 128));
+  return h->panel && shape && !getenv("BNF_PANEL_NO_H0L");
+}
+
 // carve or just measure (base == nullptr) the workspace layout
 static size_t carve(bnf_handle* h, char* base) {
   size_t off = 0;
@@ -218,7 +222,7 @@ static size_t carve(bnf_handle* h, char* base) {
   // no transposed copies (the weight-gradient contraction reads row-major, gemm_tn); the row-panel
   // kernel reads the features as MFMA A fragments from a second, fragment-major copy (H0t slot)
   // (the H0L variant -- W = 512, Fp = 64 -- stages the row-major copy in LDS instead and skips it)
-  h->h0l = h->panel && (((h->W == 512 || h->W == 1024) && h->Fp == 64) || (h->W == 256 && (h->Fp == 64 || h->Fp == 128))) && !getenv("BNF_PANEL_NO_H0L");
+  h->h0l = panel_h0l(h);
   h->H0t = (h->panel && !h->h0l) ? take((size_t)Ev * Bp * Fp * es) : nullptr;
   for (int l = 0; l < h->L; ++l) {
     h->A[l] = (h->panel || (h->fuse_last && l == h->L - 1) || (h->recompute_a0 && l == 0)) ? nullptr : take((size_t)Ev * W * (Bp + kAtPad) * es);  // A_l^T (W, Bp + pad)
@@ -251,7 +255,6 @@ static size_t carve(bnf_handle* h, char* base) {
   h->dbg_a = (float*)take(256);
   h->is_matrix = (uint8_t*)take((size_t)P);
   h->fbmeta = h->fbmeta_h.empty() ? nullptr : (int32_t*)take(h->fbmeta_h.size() * 4);
-  h->fcol = h->fcol_h.empty() ? nullptr : (int32_t*)take(h->fcol_h.size() * 4);
   if (h->cfg.mode == BNF_MODE_VI) {
     h->leaf_off = (int32_t*)take(260 * 4);
     h->leaf_id = (uint8_t*)take((size_t)P);
@@ -727,18 +730,6 @@ static void wgrad_join(bnf_handle* h) {
   }
 }
 
-// -DBNF_PANEL_DK0=1 builds + env BNF_PANEL_DK0=1: the layer-0 weight gradient inside the panel kernel (experiment;
-// MAP, W = 512, Fp = 64, no width padding: Adam clears that gradient range every step there)
-static bool panel_dk0_fused(const bnf_handle* h) {
-#if BNF_PANEL_DK0
-  static const bool on = getenv("BNF_PANEL_DK0") && atoi(getenv("BNF_PANEL_DK0")) != 0;
-  return on && h->panel && h->h0l && h->W == 512 && h->Fp == 64 && h->cfg.mode == BNF_MODE_MAP && !h->pad &&
-         h->cfg.dtype != BNF_DTYPE_FP8;     // (the fused form contracts the bf16 panels: it knows nothing of the fp8 copies)
-#else
-  (void)h;
-  return false;
-#endif
-}
 // the W x W weight gradients of layers 1 .. L-1 as ONE launch of the ring kernel (same shape, same split-K = 1):
 // 3 x 320 tiles at C3/8 are 4 rounds of the chip instead of 3 x 2
 static bool wgrad_multi_ok(const bnf_handle* h, int nmem) {
@@ -757,7 +748,7 @@ static void run_wgrad(bnf_handle* h, int nmem) {
   if constexpr (sizeof(T) == 2) {
     if (wgrad_multi_ok(h, nmem)) {
       const bool l0_first = getenv("BNF_WGRAD_ORDER") && !strcmp(getenv("BNF_WGRAD_ORDER"), "fwd");   // (see below)
-      if (l0_first && !panel_dk0_fused(h)) wgrad_after_dz<T>(h, nmem, 0);
+      if (l0_first) wgrad_after_dz<T>(h, nmem, 0);
       const int64_t Bp = h->Bp;
       GemmArgs g{};
       g.a_ld = h->W; g.a_batch = Bp * h->W; g.b_ld = h->W; g.b_batch = Bp * h->W;
@@ -776,7 +767,7 @@ static void run_wgrad(bnf_handle* h, int nmem) {
       } else {
         launch_gemm_tn<T, 1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
       }
-      if (!l0_first && !panel_dk0_fused(h)) wgrad_after_dz<T>(h, nmem, 0);
+      if (!l0_first) wgrad_after_dz<T>(h, nmem, 0);
       return;
     }
   }
@@ -785,11 +776,10 @@ static void run_wgrad(bnf_handle* h, int nmem) {
   // memory-side cache, profiles/r02w_wgrad_streams.md); after the W x W kernels have streamed their operands it does not.
   // (BNF_WGRAD_ORDER=fwd: layer 0 first, the order of rounds 1 - 3.)
   static const bool fwd_order = getenv("BNF_WGRAD_ORDER") && !strcmp(getenv("BNF_WGRAD_ORDER"), "fwd");
-  const int l_first = panel_dk0_fused(h) ? 1 : 0;
   if (fwd_order || !h->panel) {
-    for (int l = l_first; l < h->L; ++l) wgrad_after_dz<T>(h, nmem, l);
+    for (int l = 0; l < h->L; ++l) wgrad_after_dz<T>(h, nmem, l);
   } else {
-    for (int l = h->L - 1; l >= l_first; --l) wgrad_after_dz<T>(h, nmem, l);
+    for (int l = h->L - 1; l >= 0; --l) wgrad_after_dz<T>(h, nmem, l);
   }
   wgrad_join(h);
 }
@@ -945,9 +935,6 @@ static void run_pack_fragments(bnf_handle* h, const float* theta, int nmem) {
 // row-panel pipeline (bf16, depth 2): pack fragments -> featurise -> k_panel_fwd_bwd ->
 // featurise backward -> gemm_tn weight gradients
 // ---------------------------------------------------------------------------
-#ifndef BNF_PANEL_BM64
-#define BNF_PANEL_BM64 0
-#endif
 template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP, bool F0, bool C8 = false>
 static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
   constexpr int kLds = panel_lds_bytes(WN, RT, H0L, CH, FP);
@@ -996,7 +983,7 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
                       const LossSink& sink, bool fragments_packed = false) {
   const int64_t Bp = h->Bp;
   if (!fragments_packed) run_pack_fragments<bf16_t>(h, theta, nmem);   // also fills the member scalar table the next kernels read
-  if (!h->fin) {
+  {
     LaunchScope ls(h, KID_FEAT);
     dim3 grid(cdiv(h->B, kFeatRows) * (unsigned)nmem);
     const size_t lds = (size_t)kFeatRows * (h->Fp + 8) * 2;
@@ -1028,10 +1015,6 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
   pa.grad = h->gradf; pa.grad_stride = h->Pf;
   pa.loss = sink.loss; pa.loss_raw = sink.raw; pa.loss_stride = sink.stride; pa.S = h->S;
   pa.loss_scale = sink.scale; pa.lik_c = c; pa.st = sink.st;
-  pa.off_k0 = h->nd.off_kernel[0];
-  pa.dk0_fused = panel_dk0_fused(h) ? 1 : 0;
-  pa.fin = h->fin ? 1 : 0; pa.n_in = h->nd.D; pa.n_seas = 2 * h->ft.n;
-  pa.X = h->X; pa.stab = h->stab; pa.y = h->y; pa.fcol = h->fcol; pa.H0out = (bf16_t*)h->H0; pa.rs = rs;
   pa.q8 = h->q8 ? 1 : 0; pa.qscale = h->qscale;
   pa.c8 = h->c8 ? 1 : 0; pa.w8_batch = (int64_t)h->W * h->W;
   for (int l = 0; l < L; ++l) { pa.Wf8[l] = h->Wf8[l]; pa.Wb8[l] = h->Wb8[l]; }
@@ -1050,10 +1033,6 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
     } else {
       launch_panel<8, 2, false, 2>(h, pa);
     }
-  } else if (h->W == 512 && BNF_PANEL_BM64 != 0 && getenv("BNF_PANEL_BM64") && !h->h0l) {
-    // experiment (profiles/r04_panel_ab.md r04s): 64-row panels, two workgroups per CU (4 waves per SIMD, 128 registers)
-    pa.panels = (int32_t)(Bp / panel_rows(8, 2));
-    launch_panel<8, 2, false>(h, pa);
   } else if (h->W == 512) {
     pa.panels = (int32_t)(Bp / panel_rows(8, 4));
     if (h->h0l) {
@@ -1562,39 +1541,9 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
     // its contraction depth is Fp <= 128: cheaper to redo than to write + gather A_0^T
     h->recompute_a0 = !cfg->forward_only && !h->panel && want == 0 && h->L >= 2 && h->Fp <= 128;
   }
-  h->h0l = h->panel && (((h->W == 512 || h->W == 1024) && h->Fp == 64) || (h->W == 256 && (h->Fp == 64 || h->Fp == 128))) && !getenv("BNF_PANEL_NO_H0L");
+  h->h0l = panel_h0l(h);
   h->fold0 = h->h0l && h->F + 2 <= h->Fp && !(getenv("BNF_PANEL_FOLD0") && atoi(getenv("BNF_PANEL_FOLD0")) == 0);
   h->c8 = h->c8 && h->fold0;     // (the fp8-contraction kernels are instantiated for the folded forms: every BASELINE layout)
-  // (experiment builds only; not with fp8 operand storage: the fp8 feature copy H0q is written by k_featurize alone)
-  h->fin = BNF_PANEL_FIN != 0 && h->h0l && cfg->dtype != BNF_DTYPE_FP8 && getenv("BNF_PANEL_FIN") && atoi(getenv("BNF_PANEL_FIN")) != 0;
-  if (h->fin) {
-    // what every padded feature column holds (k_featurize's group loop, one entry per column) -- models.py:218-252
-    std::vector<int32_t>& m = h->fcol_h;
-    const int Fp = h->Fp;
-    m.assign((size_t)Fp * 4, 0);
-    auto put = [&](int col, int kind, int g, int a0, int b0) {
-      m[4 * col] = kind | (g << 8); m[4 * col + 1] = a0; m[4 * col + 2] = b0;
-    };
-    for (int g = 0; g < cfg->n_groups; ++g) {
-      const int c0 = cfg->group_col0[g], nc = cfg->group_ncols[g];
-      switch (cfg->group_kind[g]) {
-        case BNF_GROUP_INPUT:
-          for (int d = 0; d < cfg->n_inputs; ++d) put(c0 + d, kFcInput, g, d, 0);
-          break;
-        case BNF_GROUP_FOURIER: {
-          const int deg = nc / 2, d = cfg->group_arg[g];
-          for (int k = 0; k < deg; ++k) { put(c0 + k, kFcCos, g, d, k); put(c0 + deg + k, kFcSin, g, d, k); }
-          break;
-        }
-        case BNF_GROUP_SEASONAL:
-          for (int j = 0; j < nc; ++j) put(c0 + j, kFcSeasonal, g, j, 0);
-          break;
-        default:
-          for (int k = 0; k < nc; ++k) put(c0 + k, kFcInter, g, cfg->interact[k][0], cfg->interact[k][1]);
-      }
-    }
-    if (h->fold0) { put(h->F, kFcOne, 0, 0, 0); put(h->F + 1, kFcOne, 0, 0, 0); }
-  }
   if (h->h0l &&
       !(getenv("BNF_PANEL_FEATBWD") && atoi(getenv("BNF_PANEL_FEATBWD")) == 0)) {
     // fused featurisation backward of the H0L panel kernel: what each feature column contributes
@@ -1710,8 +1659,6 @@ int bnf_bind(bnf_handle* h, void* params, void* opt_state, void* workspace, cons
   HIPCHK(hipMemcpyAsync(h->is_matrix, mm.data(), (size_t)h->P, hipMemcpyHostToDevice, h->stream));
   if (h->fbmeta)
     HIPCHK(hipMemcpyAsync(h->fbmeta, h->fbmeta_h.data(), h->fbmeta_h.size() * 4, hipMemcpyHostToDevice, h->stream));
-  if (h->fcol)
-    HIPCHK(hipMemcpyAsync(h->fcol, h->fcol_h.data(), h->fcol_h.size() * 4, hipMemcpyHostToDevice, h->stream));
   if (h->pad) {
     HIPCHK(hipMemcpyAsync(h->pad_src, h->pad_src_h.data(), h->pad_src_h.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->fold_src, h->fold_src_h.data(), h->fold_src_h.size() * 4, hipMemcpyHostToDevice, h->stream));

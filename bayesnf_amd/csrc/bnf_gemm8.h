@@ -46,9 +46,6 @@ __device__ __forceinline__ f32x16 mfma8(const u32x2_t& h, const u32x2_t& dz, con
 // the bf16 rate), formats per operand (0 = e4m3, 1 = e5m2), scales E8M0 127 = 2^0.  A lane's 32 operand bytes are the four
 // transpose-read results of a 64-row stage back to back: lane (m, kg) byte 8 ks + b  <->  k = 16 ks + 8 kg + b for BOTH
 // operands, and the instruction pairs byte (kg, idx) of A with byte (kg, idx) of B, so the sum is the same set of products.
-#ifndef BNF_RING8_X64
-#define BNF_RING8_X64 1
-#endif
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 template <bool SWAP>
 __device__ __forceinline__ f32x16 mfma8x64(const i32x8& h, const i32x8& dz, const f32x16& c) {
@@ -373,11 +370,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_skinny8(const GemmArgs g, cons
 
 // ===========================================================================
 // gemm_tn_ring8 -- the W x W layers: gemm_tn_ring's 256 x 256 tile, eight waves of 128 x 64, four LDS-DMA stages of the
-// same 32 KiB -- but 64 batch rows each.  BNF_RING8_X64 (default): ONE K = 64 MFMA per fragment pair and stage (8 per wave
-// and barrier; a fragment = the stage's four transpose reads in an 8-register operand).  -DBNF_RING8_X64=0, the first
-// form: four K = 16 steps (32 MFMAs per wave) per barrier, 6 transpose reads per 8 MFMAs (bf16: 12), fragment sets
-// double-buffered by k step -- the set of step ks + 2 requested right after the MFMAs of step ks were issued (steps 2, 3
-// request steps 0, 1 of the NEXT stage, which the barrier at the top of this iteration certified), counted waits.
+// same 32 KiB -- but 64 batch rows each: ONE K = 64 MFMA per fragment pair and stage (8 per wave and barrier; a
+// fragment = the stage's four transpose reads in an 8-register operand).  (The first form ran four K = 16 steps, 32
+// MFMAs per wave, per barrier.)
 // ===========================================================================
 template <int TAG, bool SWAP>
 __global__ __launch_bounds__(512, 2) void gemm_tn_ring8(const GemmArgs g, const EpiArgs ep) {
@@ -438,15 +433,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_ring8(const GemmArgs g, const 
     const char* pb = pin(Bb + (int64_t)kt * kRows * g.b_ld);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-#if BNF_RING8_X64
       const uint32_t la = lds_base + (uint32_t)(buf * kStage + (wave * 2 + q) * 1024);
       dma_1k_asm(pa, src_a[q], la);
       dma_1k_asm(pb, src_b[q], la + (uint32_t)kOp);
-#else
-      char* sA = smem + buf * kStage;
-      dma_1k<BNF_TN_AUX>(pa, src_a[q], sA + (wave * 2 + q) * 1024);
-      dma_1k<BNF_TN_AUX>(pb, src_b[q], sA + kOp + (wave * 2 + q) * 1024);
-#endif
     }
   };
 
@@ -474,7 +463,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_ring8(const GemmArgs g, const 
   auto vm = [](int n) constexpr { return (n & 15) | ((n >> 4) << 14) | 0x0F70; };   // s_waitcnt vmcnt(n) only
   constexpr int kWait1 = vm(kPerWave);
   constexpr int kWaitAll = 0x0F70;
-#if BNF_RING8_X64
   // One K = 64 MFMA per fragment pair and stage (8 per wave and barrier instead of 32).  A fragment = the stage's four
   // transpose reads (k steps 0 .. 3) in one 8-register operand -- through the BUILTIN read here, so that the register
   // allocator places the four results in the operand's registers itself (assembled from inline-asm results they were
@@ -544,75 +532,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_ring8(const GemmArgs g, const 
       asm volatile("" ::: "memory");
     }
   }
-#else
-  struct Frags {
-    u32x2_t a[4], b[2];
-  };
-  auto read_k = [&](Frags& f, int sb, auto ks_tag) {
-    constexpr int ks = decltype(ks_tag)::value;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f.a[i] = lds_tr8_b64<ks * 16 * 256>(off_a[i] + sb * kStage);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) f.b[j] = lds_tr8_b64<ks * 16 * 256>(off_b[j] + sb * kStage);
-  };
-  // this set has landed (the OTHER set's six reads, issued after it, may still be in flight); `all`: nothing behind it
-  auto wait_set = [&](Frags& f, bool all) {
-    if (all) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1]));
-    else asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1]));
-  };
-  auto mma_k = [&](const Frags& f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = mfma8<SWAP>(f.a[i], f.b[j], acc[i][j]);
-  };
-  using K0 = std::integral_constant<int, 0>;
-  using K1 = std::integral_constant<int, 1>;
-  using K2 = std::integral_constant<int, 2>;
-  using K3 = std::integral_constant<int, 3>;
-
-#pragma unroll
-  for (int s = 0; s < kRgStages - 1; ++s)
-    if (kt0 + s < kt1) stage(s, kt0 + s);
-  if (kt0 + 1 < kt1) {
-    if (kt0 + 2 < kt1) __builtin_amdgcn_s_waitcnt(vm(2 * kPerWave));
-    else __builtin_amdgcn_s_waitcnt(kWait1);
-  } else {
-    __builtin_amdgcn_s_waitcnt(kWaitAll);
-  }
-  __builtin_amdgcn_s_barrier();
-  Frags f0, f1;
-  if (kt0 < kt1) {
-    read_k(f0, 0, K0{});
-    read_k(f1, 0, K1{});
-  }
-  for (int ktb = kt0; ktb < kt1; ktb += kRgStages) {
-#pragma unroll
-    for (int sb = 0; sb < kRgStages; ++sb) {
-      const int kt = ktb + sb;
-      if (kt >= kt1) break;
-      if (kt + 2 < kt1) __builtin_amdgcn_s_waitcnt(kWait1);
-      else __builtin_amdgcn_s_waitcnt(kWaitAll);
-      __builtin_amdgcn_s_barrier();
-      if (kt + kRgStages - 1 < kt1) stage((sb + kRgStages - 1) % kRgStages, kt + kRgStages - 1);
-      const bool more = kt + 1 < kt1;
-      const int sn = (sb + 1) % kRgStages;
-      wait_set(f0, false);
-      mma_k(f0);
-      read_k(f0, sb, K2{});
-      wait_set(f1, false);
-      mma_k(f1);
-      read_k(f1, sb, K3{});
-      wait_set(f0, false);
-      mma_k(f0);
-      if (more) read_k(f0, sn, K0{});
-      wait_set(f1, !more);
-      mma_k(f1);
-      if (more) read_k(f1, sn, K1{});
-    }
-  }
-
-#endif
 
   const float qs = ep.scale * (ep.qscale ? ep.qscale[e] : 1.f);
   float* out = ep.out_f32 ? ep.out_f32 + (int64_t)e * ep.f32_batch

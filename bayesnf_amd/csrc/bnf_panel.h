@@ -100,19 +100,6 @@ struct PanelArgs {
   // theta offsets of the BNF_MAX_GROUPS group scales (build_featbwd_meta in bnf_api.hip).
   const int32_t* fbmeta;
   int32_t off_lsa, n_groups, n_inputs, fb_in_group;   // fb_in_group: feature group of the raw inputs
-  // -DBNF_PANEL_DK0=1 builds (experiment, profiles/r04_panel_ab.md): layer 0's weight gradient contracted here from the
-  // dZ0 and feature panels in LDS and accumulated with f32 atomics; dZ0 is then not written and gemm_tn_skinny not run
-  int32_t off_k0, dk0_fused;
-  // fin (-DBNF_PANEL_FIN=1 builds + env BNF_PANEL_FIN=1; experiment, profiles/r04_panel_ab.md r04l): the H0L forms FEATURISE
-  // their own rows (models.py:218-252: what k_featurize does, value for value) straight into the LDS feature panel and write
-  // the row-major copy the layer-0 weight gradient reads; no k_featurize launch, no re-read of H0.  Measured: bit-identical
-  // features, and 45 - 85 us per C2 step SLOWER than the separate kernel (one workgroup per CU has nothing to hide the
-  // panel's serial start-up behind).  fcol: per padded feature column {kind | group << 8, a, b, 0}.
-  int32_t fin, n_in, n_seas;
-  const float* X; const float* stab; const float* y;
-  const int32_t* fcol;
-  bf16_t* H0out;
-  RowSrc rs;
   // q8 (compute_dtype 'fp8'): the copies this kernel leaves for the weight-gradient contractions are FP8 -- Hout[l] as OCP
   // e4m3 (un-scaled), dZ[l] as OCP e5m2 divided by a per-member power of two s_dZ, written to qscale[member] for the
   // consumers (bnf_gemm8.h) -- row-major (Bp, W) BYTES in the same buffers.  The panels in LDS and every contraction
@@ -283,9 +270,6 @@ __global__ __launch_bounds__(256) void k_pack_layers(const float* __restrict__ t
 // samples here.  Measured at C3/8 (profiles/r04_panel_ab.md r04p): 152 us against 82 + 110; neither the generator
 // (7 Philox rounds: same time) nor HBM (4.1 TB/s) nor the barriers (a barrier-free form on wave-private 32 x 32
 // sub-tiles: 157 us) bounds it; more waves per SIMD spill (104 registers).
-#ifndef BNF_VI_Z_NT
-#define BNF_VI_Z_NT 0   // 1: the f32 samples leave non-temporally (measured: 190 vs 152 us at C3/8 -- partial lines)
-#endif
 struct ViSampleArgs {
   const float* mu; const float* rho;
   int32_t P, S;
@@ -330,7 +314,7 @@ __global__ __launch_bounds__(NT) void k_vi_sample_pack(ViSampleArgs a, PackJobs 
                                       (uint32_t)(pq[i] + kEpsQuadPhase) >> 2, a.step, STREAM_VI_EPS);
 #pragma unroll
         for (int j = 0; j < 4; ++j) zv[j] = m[i][j] + sg[i][j] * n.v[j];
-        if (a.write_z) store4u<BNF_VI_Z_NT != 0>(zn + pq[i], 4, zv);
+        if (a.write_z) store4u(zn + pq[i], 4, zv);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) tl[r][c + j] = zv[j];
@@ -343,51 +327,11 @@ __global__ __launch_bounds__(NT) void k_vi_sample_pack(ViSampleArgs a, PackJobs 
 #ifndef BNF_EPI_FENCE_EVERY
 #define BNF_EPI_FENCE_EVERY 1  // scheduling fence after every 4-row group of an epilogue (2: after every second one)
 #endif
-#ifndef BNF_PANEL_PRIO
-#define BNF_PANEL_PRIO 0
-#endif
-#ifndef BNF_PANEL_NT
-#define BNF_PANEL_NT 1   // H1 / dZ1 / dZ0 leave with non-temporal stores (they are read once, by the weight-gradient kernels)
-#endif
 #ifndef BNF_PANEL_PD
 #define BNF_PANEL_PD 4
 #endif
-// round-4 steps of the panel kernel, each behind its own compile-time switch for same-box A/B builds
-// (profiles/r04_panel_ab.md):
-#ifndef BNF_PANEL_FWDS
-#define BNF_PANEL_FWDS 1     // forward epilogues: elu + 1 as ONE median per element (act_fwd_core2)
-#endif
-#ifndef BNF_PANEL_DPPSUM
-#define BNF_PANEL_DPPSUM 1   // wave-wide sums by DPP + v_readlane instead of six ds_bpermute round trips
-#endif
-#ifndef BNF_PANEL_ZPEEL
-#define BNF_PANEL_ZPEEL 1    // contractions start from a zero C operand (no 128 v_mov per contraction and wave)
-#endif
-#ifndef BNF_PANEL_PRE0
-#define BNF_PANEL_PRE0 0     // (measured: no gain, r04a) layer-0 weights and biases requested BEFORE the barrier that completes the staged feature panel
-#endif
-#ifndef BNF_PANEL_SADDR
-#define BNF_PANEL_SADDR 1    // weight fragments of the W x W contractions: uniform base in SGPRs + the lane's 32-bit offset (no 64-bit VALU address per load)
-#endif
-#ifndef BNF_PANEL_CPRIO
-#define BNF_PANEL_CPRIO 1    // (r04d: -0.4 %) 1: the second-dispatched waves run the contractions at priority 1; 2: the first-dispatched ones do
-#endif
-#ifndef BNF_PANEL_FIN
-#define BNF_PANEL_FIN 0      // experiment: the H0L forms featurise their own rows; -DBNF_PANEL_FIN=1 + env BNF_PANEL_FIN=1
-#endif
-#ifndef BNF_PANEL_DK0
-#define BNF_PANEL_DK0 0      // experiment: dK_0 = H0^T dZ0 inside the panel kernel (f32 atomics), env BNF_PANEL_DK0=1 at run time
-#endif
-#ifndef BNF_PANEL_PKCLAMP
-#define BNF_PANEL_PKCLAMP 1  // backward epilogues: min(e, 1) of an element pair by one packed multiply with the clamp modifier
-#endif
-#ifndef BNF_PANEL_L1T
-#define BNF_PANEL_L1T 1      // round 5: the LAST hidden layer on transposed tiles with its activation evaluated ONCE (see k_panel_fwd_bwd)
-#endif
-#ifndef BNF_PANEL_FAIR
-#define BNF_PANEL_FAIR 0     // round 6 experiment (measured: no gain, profiles/r06_panel_ab.md): the two waves of a SIMD take turns at priority through the VALU-only epilogues (see fair_prio)
-#endif
 constexpr int kPanelPD = BNF_PANEL_PD;       // weight fragments in flight per stream; must divide W / 16 (2: +2 % panel time, 8: equal -- gpurun_out/r03ar)
+constexpr int kAuxNT = 2;                    // aux bits of a raw buffer store: non-temporal (H1 / dZ1 / dZ0 are read once, by the weight-gradient kernels)
 
 // RT = 32-row tiles per wave (4: one workgroup per CU, 256 registers; 2: two workgroups per CU, 128)
 __host__ __device__ constexpr int panel_rows(int wn, int rt) { return 32 * rt * (8 / wn); }
@@ -413,21 +357,6 @@ __device__ __forceinline__ int opaque_lane(int x) {
   return x;
 }
 
-__device__ __forceinline__ ActCore2 panel_act_core2(f32x2 t) {   // the backward epilogues' activation core
-#if BNF_PANEL_PKCLAMP
-  return act_core2_pkclamp(t);
-#else
-  return act_core2(t);
-#endif
-}
-__device__ __forceinline__ float panel_wave_sum(float v) {
-#if BNF_PANEL_DPPSUM
-  return wave_sum_dpp(v);
-#else
-  return wave_sum(v);
-#endif
-}
-
 // workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also drains
 // vmcnt, i.e. would wait for the panel copies to HBM (128 KiB per workgroup) at every phase change
 __device__ __forceinline__ void lds_barrier() {
@@ -446,31 +375,21 @@ __device__ __forceinline__ void lds_barrier() {
 struct PanelRing {
   bf16x8 fb[kPanelPD][2];
 };
-// One weight fragment (16 bytes per lane) at the wave-uniform address wp + soff, lane offset loff.  BNF_PANEL_SADDR: as a
+// One weight fragment (16 bytes per lane) at the wave-uniform address wp + soff, lane offset loff, as a
 // raw buffer load -- the resource (base, in SGPRs) is made once per contraction, the fragment index goes into the scalar
 // offset and the lane offset into the 32-bit VGPR offset: no VALU address arithmetic per load (the flat-pointer form
 // costs a 64-bit v_lshl_add_u64 per load, four VALU slots per k step and wave next to eight MFMAs).
 struct PanelW {
-#if BNF_PANEL_SADDR
   __amdgpu_buffer_rsrc_t rsrc;
-#endif
-  const char* base;
 };
 __device__ __forceinline__ PanelW panel_wbase(const char* wp) {
   PanelW w;
-  w.base = wp;
-#if BNF_PANEL_SADDR
   // raw buffer (stride 0), 2 GiB window, gfx9 DATA_FORMAT = 32 (word 3 = 0x00020000)
   w.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wp), 0, 0x7fffffff, 0x00020000);
-#endif
   return w;
 }
 __device__ __forceinline__ bf16x8 panel_wload(const PanelW& w, uint32_t soff, uint32_t loff) {
-#if BNF_PANEL_SADDR
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w.rsrc, loff, soff, 0));
-#else
-  return *reinterpret_cast<const bf16x8*>(w.base + soff + loff);
-#endif
 }
 __device__ __forceinline__ void panel_prefetch(PanelRing& ring, const char* wp, int nt0, int KS, int lane) {
   const PanelW w = panel_wbase(wp);
@@ -482,11 +401,11 @@ __device__ __forceinline__ void panel_prefetch(PanelRing& ring, const char* wp, 
     ring.fb[p][1] = panel_wload(w, o1 + p * 1024u, loff);
   }
 }
-// ZERO: the accumulators are written, not accumulated into -- the first k step's MFMAs take a literal zero C operand
+// The accumulators are written, not accumulated into -- the first k step's MFMAs take a literal zero C operand
 // (an inline constant), which saves the 16 RT v_mov per slab a zeroed accumulator costs before the first MFMA can issue.
 // SWAP: the operands in swapped roles (weights as A, panel as B): acc[i][j] holds the TRANSPOSED tile -- lane <-> panel
 // row i * 32 + lane % 32, register r <-> column j * 32 + 8 (r / 4) + 4 (lane / 32) + r % 4.
-template <int KPITCH_B, int RT, bool ZERO, bool SWAP, typename Side>
+template <int KPITCH_B, int RT, bool SWAP, typename Side>
 __device__ __forceinline__ void panel_contract(f32x16 (&acc)[RT][2], const char* prow, const char* wp, int nt0, int KS,
                                                int lane, PanelRing& ring, Side side) {
   constexpr int PD = kPanelPD;
@@ -539,9 +458,9 @@ __device__ __forceinline__ void panel_contract(f32x16 (&acc)[RT][2], const char*
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  if constexpr (ZERO) group(0, std::true_type{});
+  group(0, std::true_type{});
 #pragma unroll 1
-  for (int ks0 = ZERO ? PD : 0; ks0 < KS; ks0 += PD) group(ks0, std::false_type{});
+  for (int ks0 = PD; ks0 < KS; ks0 += PD) group(ks0, std::false_type{});
 }
 
 // The same contraction on the block-scaled fp8 MFMA (PanelArgs.c8): acc[RT][2] = P8[rows of this wave][0 .. 64 KS64) . W8
@@ -654,7 +573,7 @@ __device__ __forceinline__ void l0_mma(f32x16& a0, const L0Blk& bk) {
 // roles SWAPPED (weights as A, panel rows as B): a lane then owns ONE row and four consecutive hidden units per
 // register group, and the bf16 panel store is one ds_write_b64 per four elements instead of four ds_write_b16.
 template <int WN, int RT, bool H0L, bool DEEP = false, int CH = 1, int FP = 64, bool F0 = false, bool C8 = false>
-__global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_panel_fwd_bwd(const PanelArgs a) {   // (4: the r04s experiment form only)
+__global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   static_assert(!F0 || H0L, "the folded layer 0 needs the LDS feature panel");
   constexpr int W = 64 * WN * CH, RB = 8 / WN, WR = 32 * RT, BM = WR * RB;   // WR = rows per wave
   constexpr int kSlabs = WN * CH;           // 64-column slabs of the layer
@@ -685,32 +604,10 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   const int wave = __builtin_amdgcn_readfirstlane(tid_k >> 6);
   const int rb = wave / WN, cs = wave % WN;
   const int rbase = rb * WR;
-  // FAIR (round 6 experiment, -DBNF_PANEL_FAIR=1; profiles/r06_panel_ab.md): in a VALU-only epilogue the SIMD arbitrates its
-  // two waves by age -- the first-dispatched wave takes every slot it can use and reaches the barrier first (phase clocks:
-  // layer-1 forward 10.9k cycles for wave 0, 16.9k for wave 7 from the same barrier).  Would taking turns at priority, tile
-  // by tile (chunk c at priority (c + half) % 2), end both earlier?  Measured: no -- wave 0 slows to 13.2k, wave 7 stays at
-  // 16.9k, the step is +0.4 %: the phase is bound by the SUM of the two waves' issue, however it is shared.
-  auto fair_prio = [&](int chunk) {
-#if BNF_PANEL_FAIR
-    if (((chunk & 1) != 0) != (wave >= 4)) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-#else
-    (void)chunk;
-#endif
-  };
-  auto fair_prio_end = [&]() {
-#if BNF_PANEL_FAIR
-    __builtin_amdgcn_s_setprio(0);
-#endif
-  };
+  // (The two waves of a SIMD taking turns at priority through the VALU-only epilogues: no gain, profiles/r06_panel_ab.md;
+  // a static priority for the second-dispatched half of the workgroup: not kept, profiles/r03_panel_ab.md.)
   auto slab = [&](int hc) { return cs * CH + hc; };          // this wave's hc-th 64-column slab
   const int KS0 = a.Fp / 16;
-#if BNF_PANEL_PRIO
-  // static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per
-  // SIMD, item 4): the younger wave of every SIMD loses the issue arbitration in every phase
-  // (measured: 1313-1323 us against 1309-1315 us without, same box -- not kept, profiles/r03_panel_ab.md)
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   // (A persistent variant -- `ppw` consecutive panels per workgroup, the next panel's features requested a
   // trip ahead -- was built and measured: 1390-1413 us for every ppw in {1, 2, 5, 10, 20} against 1355-1363 us
   // for this one-panel-per-workgroup form on the same box: the loop costs registers (hipcc hoists the
@@ -752,7 +649,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   }
   const float inv_qdz = 1.0f / q_dz;     // (a power of two: exact)
   // the row phase's target value, fetched now (one thread per row; rows >= B read nothing)
-  const float y_pre = (!(BNF_PANEL_FIN && H0L && a.fin) && tid < BM && m0 + tid < a.B) ? a.ybat[(int64_t)e * a.row_batch + m0 + tid] : 0.f;
+  const float y_pre = (tid < BM && m0 + tid < a.B) ? a.ybat[(int64_t)e * a.row_batch + m0 + tid] : 0.f;
 
   float* s_grp = s_sc + 64;                 // [BNF_MAX_GROUPS + BNF_MAX_INPUTS] sums of the fused featurisation backward
   float* s_gfac = s_sc + 88;                // [BNF_MAX_GROUPS] sigmoid(scale_g) / softplus(scale_g) ...
@@ -823,7 +720,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
       else
         o = u32x4{bf16x4_to_fp8(v[u][0][0], v[u][0][1], 1.f), bf16x4_to_fp8(v[u][0][2], v[u][0][3], 1.f),
                   bf16x4_to_fp8(v[u][1][0], v[u][1][1], 1.f), bf16x4_to_fp8(v[u][1][2], v[u][1][3], 1.f)};
-      __builtin_amdgcn_raw_buffer_store_b128(o, rs, (uint32_t)(row * W + p4 * 16), 0, BNF_PANEL_NT ? 2 : 0);
+      __builtin_amdgcn_raw_buffer_store_b128(o, rs, (uint32_t)(row * W + p4 * 16), 0, kAuxNT);
     }
   };
   // C8: a 32-row x 64-column block of an FP8 panel image (H_1 as e4m3, dZ_L as e5m2 / s_dZ) is already what the
@@ -841,7 +738,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int pc = lane + 64 * u, row = pc >> 2, p4 = pc & 3;
-      __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)(row * W + p4 * 16), 0, BNF_PANEL_NT ? 2 : 0);
+      __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)(row * W + p4 * 16), 0, kAuxNT);
     }
   };
   // C8, lane <-> column layouts (store_pair_pk's counterpart): the elements (row r, column c) and (row r + 1, column c) of
@@ -879,39 +776,17 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
       const int idx = L.lane + 64 * u;
       v[u] = *reinterpret_cast<const u32x4*>(sp + (idx >> 3) * kPitchE + (idx & 7) * 8);
     }
-#if BNF_PANEL_SADDR
     // raw buffer stores: the block's (uniform) address is the resource base, a lane's place in the block its 32-bit
     // offset -- no 64-bit VALU address per store (aux 2 = non-temporal)
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int idx = L.lane + 64 * u;
-      __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)((idx >> 3) * W * 2 + (idx & 7) * 16), 0, BNF_PANEL_NT ? 2 : 0);
+      __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)((idx >> 3) * W * 2 + (idx & 7) * 16), 0, kAuxNT);
     }
-#else
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int idx = L.lane + 64 * u;
-#if BNF_PANEL_NT
-      __builtin_nontemporal_store(v[u], reinterpret_cast<u32x4*>(d + (int64_t)(idx >> 3) * W + (idx & 7) * 8));
-#else
-      *reinterpret_cast<u32x4*>(d + (int64_t)(idx >> 3) * W + (idx & 7) * 8) = v[u];
-#endif
-    }
-#endif
   };
 
   f32x16 accs[CH][RT][2];   // [slab][row tile][column tile]; the phases below see one slab at a time as `acc`
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int hc = 0; hc < CH; ++hc)
-#pragma unroll
-      for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) accs[hc][i][j][r] = 0.f;
-  };
   // Layer-0 pre-activations of the 32 x 32 tile (row block i, column half j) of this wave,
   // a0 = H0 K0 (un-scaled).  `blk` enters holding the first four k steps of tile t = 2 i + j and
   // leaves holding those of tile t + 1 (in flight during the caller's epilogue).
@@ -974,46 +849,13 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   };
 
   // =============================== layer 0 forward -> H1 panel ===============================
-  // (BNF_PANEL_PRE0) slab 0's layer-0 weight fragments and biases do not depend on the staged features: requested before
-  // the barrier, their L2 latency runs under the feature panel's HBM latency instead of behind it
-  constexpr bool kPre0 = BNF_PANEL_PRE0 != 0 && H0L;
-  const LaneCtx Lpre = lane_ctx(0);
-  float gb_pre[2] = {0.f, 0.f};
-  if constexpr (kPre0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) gb_pre[j] = th[a.off_bias[0] + slab(0) * 64 + j * 32 + Lpre.frow];
-    l0_weights(Lpre);
-  }
+  // (Requesting slab 0's layer-0 weights and biases before the staging barrier: no gain, profiles/r04_panel_ab.md r04a.
+  // What is left of it is this lane context that nothing reads: without the statement hipcc orders and allocates the
+  // H0L forms differently (the code is dead, the optimiser's input order is not), so it leaves with a change that is
+  // measured on the device, not with this one.)
+  (void)lane_ctx(0);
   if constexpr (H0L) {
-   if (BNF_PANEL_FIN && a.fin) {
-    // ---- featurise this panel's rows into LDS (what k_featurize<bf16_t> computes, value for value) -----------------
-    // A lane owns a ROW, a wave a block of CPT consecutive columns of 64 rows: which column holds what is then uniform
-    // across the wave -- metadata and group scales by scalar loads, no divergence (a first version with four lanes per
-    // row and 16 columns each diverged four ways per column and cost 105 us per launch against the 37 us of the kernel
-    // it replaced: profiles/r04_panel_ab.md r04l).  Inputs u_d = x_d / (input scale e^lsa_d) (the member's scalar table),
-    // Fourier columns cos / sin(2 pi 2^k u_d) / (k + 1) by the hardware v_cos / v_sin on the fractional part, seasonal
-    // columns from the data-constant table, interactions u_p u_q, every group times softplus(scale_g); the ones columns
-    // of the folded layer 0; zero padding.  The row's target goes to s_dv (read by the row phase).
-    constexpr int RG = BM / 64, PARTS = 8 / RG, CPT = FP / PARTS;    // row groups of 64, waves per row group, columns per wave
-    static_assert(BM % 64 == 0 && CPT % 8 == 0 && CPT * PARTS == FP, "feature panel geometry");
-    const int part = wave % PARTS;                                   // uniform
-    const int r = (wave / PARTS) * 64 + (tid & 63);
-    const int m = m0 + r;
-    float vals[CPT];
-    const bool live = m < a.B;
-    const int64_t row = live ? row_of(a.rs, e, m) : 0;            // (dead rows compute on row 0 and store zeros)
-    const float y_here = (a.y && part == 0 && live) ? a.y[row] : 0.f;
-    FeatIn fi;
-    fi.X = a.X; fi.stab = a.stab; fi.sc = sc; fi.fcol = a.fcol; fi.n_in = a.n_in; fi.n_seas = a.n_seas;
-    featurize_cols<CPT>(fi, row, live, part * CPT, vals);
-    if (part == 0) s_dv[r] = y_here;
-#pragma unroll
-    for (int ch = 0; ch < CPT / 8; ++ch) {
-      const u32x4 w = {pack_bf16x2(vals[8 * ch], vals[8 * ch + 1]), pack_bf16x2(vals[8 * ch + 2], vals[8 * ch + 3]),
-                       pack_bf16x2(vals[8 * ch + 4], vals[8 * ch + 5]), pack_bf16x2(vals[8 * ch + 6], vals[8 * ch + 7])};
-      *reinterpret_cast<u32x4*>(const_cast<char*>(h0s) + r * kH0Pitch + (part * CPT + 8 * ch) * 2) = w;
-    }
-   } else {
+    // (Featurising the rows here instead: bit-identical, 45 - 85 us per C2 step slower, profiles/r04_panel_ab.md r04l.)
     // feature panel -> LDS (row-major source written by k_featurize, 16-byte chunks, 8 per row)
     const bf16_t* src = a.H0rm + (int64_t)e * a.h0_batch + (int64_t)m0 * FP;
     constexpr int kCpr = FP / 8;              // 16-byte chunks per feature row
@@ -1023,34 +865,21 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
       *reinterpret_cast<u32x4*>(const_cast<char*>(h0s) + (q / kCpr) * kH0Pitch + (q % kCpr) * 16) =
           *reinterpret_cast<const u32x4*>(src + (int64_t)(q / kCpr) * FP + (q % kCpr) * 8);
     }
-   }
   }
   if (BNF_MARK0_AT == 0) BNF_MARK(a, 0);
   if constexpr (H0L) lds_barrier();     // the staged feature panel is complete
   if (BNF_MARK0_AT == 2) BNF_MARK(a, 0);
-  if constexpr (H0L) {
-    if (BNF_PANEL_FIN && a.fin) {   // the row-major (Bp, Fp) copy the layer-0 weight gradient reads: whole 16-byte chunks, rows >= B are zero
-      constexpr int kCpr = FP / 8;
-      bf16_t* dst = a.H0out + (int64_t)e * a.h0_batch + (int64_t)m0 * FP;
-#pragma unroll
-      for (int c = 0; c < (BM * kCpr) / 512; ++c) {
-        const int q = tid + c * 512;
-        *reinterpret_cast<u32x4*>(dst + (int64_t)(q / kCpr) * FP + (q % kCpr) * 8) =
-            *reinterpret_cast<const u32x4*>(h0s + (q / kCpr) * kH0Pitch + (q % kCpr) * 16);
-      }
-    }
-  }
 #pragma unroll
   for (int hc = 0; hc < CH; ++hc) {
     const int cbase = slab(hc) * 64;
-    const LaneCtx L = (kPre0 && hc == 0) ? Lpre : lane_ctx(hc);
+    const LaneCtx L = lane_ctx(hc);
     const int frow = L.frow, kg = L.kg;
     const float gs = gamma0 * inv_sf * kLog2e;     // t = A0 log2(e): the activation core works on it (act_core2)
     float gb[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      gb[j] = BNF_ABL(a, 64) ? 0.1f : gamma0 * kLog2e * ((kPre0 && hc == 0) ? gb_pre[j] : th[a.off_bias[0] + cbase + j * 32 + frow]);
-    if (!BNF_ABL(a, 64) && !(kPre0 && hc == 0)) l0_weights(L);
+      gb[j] = BNF_ABL(a, 64) ? 0.1f : gamma0 * kLog2e * th[a.off_bias[0] + cbase + j * 32 + frow];
+    if (!BNF_ABL(a, 64)) l0_weights(L);
     // epilogue of one 32 x 32 tile: t = A0 log2(e) -> H1 = act(A0) -> LDS panel
     auto l0_epilogue = [&](const f32x16& a0, int i, int j) {
       if constexpr (F0) {
@@ -1063,14 +892,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
 #pragma unroll
           for (int q = 0; q < 4; q += 2) {
             const f32x2 tv = {a0[rg * 4 + q], a0[rg * 4 + q + 1]};
-#if BNF_PANEL_FWDS
             const ActFwd2 c = act_fwd_core2(tv);
             hq[q >> 1] = ak.c1 * c.r + (ak.alpha * c.s + ak.c0);
-#else
-            const ActCore2 c = act_core2(tv);
-            const f32x2 s = kLn2 * c.mxt + c.dl;
-            hq[q >> 1] = ak.c1 * c.r + (ak.alpha * s + ak.c0);
-#endif
           }
           if constexpr (C8) {      // H_1 leaves as e4m3 into the fp8 panel image: four consecutive hidden units = one dword
             int pk = __builtin_amdgcn_cvt_pk_fp8_f32(hq[0].x, hq[0].y, 0, false);
@@ -1092,14 +915,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
           const f32x2 tv = f32x2{a0[rg * 4 + q], a0[rg * 4 + q + 1]} * gs + gbj;
           f32x2 h = tv;
           if (!BNF_ABL(a, 2)) {
-#if BNF_PANEL_FWDS
             const ActFwd2 c = act_fwd_core2(tv);
             h = ak.c1 * c.r + (ak.alpha * c.s + ak.c0);
-#else
-            const ActCore2 c = act_core2(tv);
-            const f32x2 s = kLn2 * c.mxt + c.dl;
-            h = ak.c1 * c.r + (ak.alpha * s + ak.c0);
-#endif
           }
           if (!BNF_ABL(a, 4)) store_pair_pk(tile + (lr + q) * kPitchE + lc, tile + (lr + q + 1) * kPitchE + lc, h.x, h.y);
         }
@@ -1115,14 +932,11 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
 #pragma unroll 1
       for (int i = 0; i < RT; ++i) {
         l0_tile(L, a0b[1], i, 1);
-        fair_prio(0);
         l0_epilogue(a0b[0], i, 0);
         if (i > 0) block_to_global(L, a.Hout[0], i - 1, cbase);
         if (i + 1 < RT) l0_tile(L, a0b[0], i + 1, 0);
-        fair_prio(1);
         l0_epilogue(a0b[1], i, 1);
       }
-      fair_prio_end();
       block_to_global(L, a.Hout[0], RT - 1, cbase);
     } else {
 #pragma unroll 1
@@ -1157,40 +971,32 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
     const char* prow8 = smem + (rbase + (lane & 31)) * kPitch8 + (lane >> 5) * 32;
     // s_dZ = 2^k exactly: its E8M0 byte is the float's own exponent field
     const int pscale = kBf8 ? (int)((__float_as_uint(q_dz) >> 23) & 0xffu) : 127;
-#if BNF_PANEL_CPRIO
-    if ((BNF_PANEL_CPRIO == 1) == (wave >= 4)) __builtin_amdgcn_s_setprio(1);
-#endif
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int hc = 0; hc < CH; ++hc)
       panel_contract8<kPitch8, RT, decltype(swap_tag)::value, kBf8>(accs[hc], prow8, wp8, 2 * slab(hc), W / 64, lane, pscale);
-#if BNF_PANEL_CPRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
   };
   auto contract_all_t = [&](const char* wp, auto swap_tag) {   // accs[hc] (+)= panel . W[:, slab hc] for every slab
     const LaneCtx L = lane_ctx();
-#if BNF_PANEL_CPRIO
-    if ((BNF_PANEL_CPRIO == 1) == (wave >= 4)) __builtin_amdgcn_s_setprio(1);
-#endif
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int hc = 0; hc < CH; ++hc)
-      panel_contract<kPitchB, RT, BNF_PANEL_ZPEEL != 0, decltype(swap_tag)::value>(accs[hc], L.prow, wp, 2 * slab(hc), KS1, L.lane,
+      panel_contract<kPitchB, RT, decltype(swap_tag)::value>(accs[hc], L.prow, wp, 2 * slab(hc), KS1, L.lane,
                                                                                   ring[hc], [](int) {});
-#if BNF_PANEL_CPRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
   };
   // L1T: the copy of the dZ_L panel to HBM (for the weight gradient).  The backward epilogue of the last layer has no
   // arithmetic left to hide 128 KiB of stores behind (HBM takes ~13 B/clk/CU with every CU storing: the epilogue measured
   // 10.4k cycles with the copy inside it, 7.6k without), and stores issued DURING the next contraction sit in front of its
   // weight-ring loads in the wave's in-order vmcnt (+2.7k cycles on that contraction: profiles/r05_panel_ab.md).  But the
-  // contraction that reads this panel is finished early by the four waves that run it at priority (BNF_PANEL_CPRIO: the
-  // second-dispatched half; 11k against 17.5k cycles), which then sit at the barrier: THEY copy the whole panel -- their own
+  // contraction that reads this panel is finished early by the four waves that run it at priority (the second-dispatched
+  // half, wave >= 4; 11k against 17.5k cycles), which then sit at the barrier: THEY copy the whole panel -- their own
   // 64 columns and those of the wave they share a SIMD with -- while the other four are still multiplying.  Only LDS
   // reads (complete before the barrier: lds_barrier) and fire-and-forget stores.
   auto copy_panel_by_early_waves = [&](bf16_t* dst) {
     if (BNF_ABL(a, 8)) return;
-    if ((BNF_PANEL_CPRIO == 2) == (wave >= 4)) return;       // (the waves that ran the contraction WITHOUT priority: busy)
+    if (wave < 4) return;       // (the waves that ran the contraction WITHOUT priority: busy)
     const int lane = opaque_lane(tid) & 63;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -1222,7 +1028,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
 #pragma unroll
         for (int u = 0; u < 4 * CH; ++u) {
           const int idx = lane + 64 * u, row = i * 32 + (idx >> (3 + (CH - 1))), pc = idx & (8 * CH - 1);
-          __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)(row * W * 2 + pc * 16), 0, BNF_PANEL_NT ? 2 : 0);
+          __builtin_amdgcn_raw_buffer_store_b128(v[u], rs, (uint32_t)(row * W * 2 + pc * 16), 0, kAuxNT);
         }
       }
     }
@@ -1244,7 +1050,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   // both directions are whole 1 KiB wave accesses (the layer pipeline stores A_l^T, same rounding).
 #pragma unroll 1
   for (int l = 1; DEEP && l < LL; ++l) {
-    if (!BNF_PANEL_ZPEEL) zero_acc();
     if constexpr (c8) contract_all8(a.Wf8[l] + (int64_t)e * a.w8_batch, std::false_type{}, std::false_type{});
     else contract_all(wfl(l));
     lds_barrier();
@@ -1276,13 +1081,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
             for (int q = 0; q < 4; q += 2) {
               const f32x2 tv = f32x2{acc[i][j][rg * 4 + q], acc[i][j][rg * 4 + q + 1]} * gs + gb[j];
               pw[rg * 2 + (q >> 1)] = pack_bf16x2(tv.x, tv.y);
-#if BNF_PANEL_FWDS
               const ActFwd2 c = act_fwd_core2(tv);
               const f32x2 s = c.s;
-#else
-              const ActCore2 c = act_core2(tv);
-              const f32x2 s = kLn2 * c.mxt + c.dl;
-#endif
               const f32x2 h = ak.c1 * c.r + (ak.alpha * s + ak.c0);
               if constexpr (C8) store_pair_p8(lr + q, lc, h.x, h.y, std::false_type{});
               else store_pair_pk(tile_i + (8 * rg + q) * kPitchE + lc, tile_i + (8 * rg + q + 1) * kPitchE + lc, h.x, h.y);
@@ -1317,8 +1117,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   // (not CH = 2, the W = 1024 form: both slabs' accumulators + the column constants spill; not WN = 4, the W = 256 forms: a
   // wave holds half as many elements, the column-sum MFMAs and their atomics -- two row blocks each -- weigh twice as much:
   // C5/8 10.89k -> 10.79k member-steps/s same box, three alternations, profiles/r05_panel_ab.md)
-  constexpr bool kL1T = BNF_PANEL_L1T != 0 && CH == 1 && WN == 8;
-  if (!BNF_PANEL_ZPEEL) zero_acc();
+  constexpr bool kL1T = CH == 1 && WN == 8;
   if constexpr (c8)
     contract_all8(a.Wf8[LL] + (int64_t)e * a.w8_batch, std::integral_constant<bool, kL1T>{}, std::false_type{});
   else
@@ -1376,7 +1175,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         f32x2 ds2 = {0.f, 0.f}, dr2 = {0.f, 0.f}, du2 = {0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          fair_prio(2 * i + j);
           bf16_t* rowp = tile + (rbase + i * 32 + frow) * kPitchE + cbase + j * 32 + 4 * kg;
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
@@ -1386,7 +1184,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
               const f32x2 raw = {acc[i][j][rg * 4 + q], acc[i][j][rg * 4 + q + 1]};
               const f32x2 kp = kvp[j][rg * 2 + (q >> 1)];
               const f32x2 tv = raw * gs + gbp[j][rg * 2 + (q >> 1)];
-              const ActCore2 c = panel_act_core2(tv);
+              const ActCore2 c = act_core2_pkclamp(tv);
               const f32x2 sv = kLn2 * c.mxt + c.dl;                                   // elu + 1
               hq[q >> 1] = ak.c1 * c.r + (ak.alpha * sv + ak.c0);                   // act(A)
               ds2 += kp * sv;
@@ -1412,7 +1210,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         wrow[hc][i] = (dsv + 2.f * drv) * inv_g1;     // sum_c (k_o / sqrt W) (elu - tanh + 2)
         urow[hc][i] = duv;
       }
-      fair_prio_end();
     }
   } else {
   // ---- A1 = gamma1 (acc / sqrt W + b1) kept in the accumulators; row dots act(A1) . k_o ----
@@ -1435,7 +1232,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
       ka[j] = kov * ak.alpha; kc1[j] = kov * ak.c1;
       ksum += kov;
     }
-    ksum = panel_wave_sum(kg == 0 ? ksum : 0.f);           // sum of k_o over this slab's 64 columns
+    ksum = wave_sum_dpp(kg == 0 ? ksum : 0.f);           // sum of k_o over this slab's 64 columns
     ksum_wave += ksum;
     if (hc == CH - 1 && lane == 0) s_sc[48 + wave] = ksum_wave;   // (read by thread 0 after the barriers below)
     ksum *= ak.c0;
@@ -1456,13 +1253,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
               const f32x2 tv = raw * gs + gb[j];
               acc[i][j][rg * 4 + q] = tv.x;
               acc[i][j][rg * 4 + q + 1] = tv.y;
-#if BNF_PANEL_FWDS
               const ActFwd2 c = act_fwd_core2(tv);
               const f32x2 s = c.s;
-#else
-              const ActCore2 c = act_core2(tv);
-              const f32x2 s = kLn2 * c.mxt + c.dl;
-#endif
               f32x2 pq = {pd[q], pd[q + 1]};
               pq = ka[j] * s + pq;
               pq = kc1[j] * c.r + pq;
@@ -1510,7 +1302,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
     float ll = 0.f, s_doutv = 0.f, s_dvsum = 0.f, s_par = 0.f, s_infl = 0.f;
     if (tid < BM) {
       const int m = m0 + tid;
-      const float y_row = (BNF_PANEL_FIN && H0L && a.fin) ? s_dv[tid] : y_pre;   // (fin: the featurisation left the row's target here)
       float vsum = 0.f;
 #pragma unroll
       for (int c = 0; c < kSlabs; ++c) vsum += s_part[tid * kSlabs + c];
@@ -1521,13 +1312,13 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         a.out[(int64_t)e * a.out_batch + m] = outv;
         RowLoss rl;
         if (a.obs == BNF_OBS_NORMAL) {   // row_loss_eval's NORMAL branch on the precomputed member scalars
-          const float z = (y_row - outv) * inv_sigma;
+          const float z = (y_pre - outv) * inv_sigma;
           rl.ll = -0.5f * z * z + ll_const;
           rl.dout = -a.lik_c * z * inv_sigma;
           rl.d_par = -a.lik_c * (z * z - 1.0f) * inv_sigma * e_lns;
           rl.d_infl = 0.f;
         } else {
-          rl = row_loss_eval(a.obs, th, a.off_lns, a.off_shape, a.off_infl, y_row, outv, a.lik_c);
+          rl = row_loss_eval(a.obs, th, a.off_lns, a.off_shape, a.off_infl, y_pre, outv, a.lik_c);
         }
         ll = rl.ll; s_par = rl.d_par; s_infl = rl.d_infl;
         s_doutv = rl.dout * v;
@@ -1536,8 +1327,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
       }
       s_dv[tid] = dvv;
       if constexpr (kL1T) reinterpret_cast<bf16_t*>(s_col)[tid].bits = f32_to_bf16_bits(dvv);   // A fragments of d k_o = dv^T H (s_col is idle until the next layer's sums)
-      const float t0 = panel_wave_sum(ll), t1 = panel_wave_sum(s_doutv), t2 = panel_wave_sum(s_dvsum), t3 = panel_wave_sum(s_par),
-                  t4 = panel_wave_sum(s_infl);
+      const float t0 = wave_sum_dpp(ll), t1 = wave_sum_dpp(s_doutv), t2 = wave_sum_dpp(s_dvsum), t3 = wave_sum_dpp(s_par),
+                  t4 = wave_sum_dpp(s_infl);
       if ((tid & 63) == 0) {
         float* q = s_sc + wave * 5;
         q[0] = t0; q[1] = t1; q[2] = t2; q[3] = t3; q[4] = t4;
@@ -1648,8 +1439,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         }
       }
       // both halves of the wave hold every row's dots: count them once
-      wsa_all += panel_wave_sum(kg == 0 ? wsa : 0.f);
-      wsg_all += panel_wave_sum(kg == 0 ? (kLn2 / gamma1) * wsg : 0.f);
+      wsa_all += wave_sum_dpp(kg == 0 ? wsa : 0.f);
+      wsg_all += wave_sum_dpp(kg == 0 ? (kLn2 / gamma1) * wsg : 0.f);
       if (hc == CH - 1 && lane == 0) {
         s_sc[32 + wave * 2] = wsa_all;
         s_sc[33 + wave * 2] = wsg_all;
@@ -1697,7 +1488,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
             f32x2 tv = {acc[i][j][rg * 4 + q], acc[i][j][rg * 4 + q + 1]};
             asm volatile("" : "+v"(tv));
             const f32x2 dv2 = {dv4[q], dv4[q + 1]};
-            const ActCore2 c = panel_act_core2(tv);
+            const ActCore2 c = act_core2_pkclamp(tv);
             const f32x2 s = kLn2 * c.mxt + c.dl;
             const f32x2 dg = gkc[j] * (c.r - c.r * c.r) + gka[j] * c.dl;
             const f32x2 z = dv2 * dg;
@@ -1737,8 +1528,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         s_col[(RB + rb) * W + cbase + j * 32 + lane] = k;
       }
     }
-    wsa_all += panel_wave_sum(wsa);
-    wsg_all += panel_wave_sum(wsg);
+    wsa_all += wave_sum_dpp(wsa);
+    wsg_all += wave_sum_dpp(wsg);
     if (hc == CH - 1 && lane == 0) {
       s_sc[32 + wave * 2] = wsa_all;
       s_sc[33 + wave * 2] = wsg_all;
@@ -1800,7 +1591,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
   // dZ_l = gamma_l (dH_{l+1} / sqrt W) act'(A_l) with t_l read back from where this wave parked it
 #pragma unroll 1
   for (int l = LL - 1; DEEP && l >= 1; --l) {
-    if (!BNF_PANEL_ZPEEL) zero_acc();
     if constexpr (c8) contract_all8(a.Wb8[l + 1] + (int64_t)e * a.w8_batch, std::false_type{}, std::true_type{});
     else contract_all(wbl(l + 1));
     const LaneCtx L = lane_ctx();
@@ -1843,7 +1633,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
               const uint32_t w = cur[rg >> 1][(rg & 1) * 2 + (q >> 1)];
               const f32x2 tv = {__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
               const f32x2 raw = {acc[i][j][rg * 4 + q], acc[i][j][rg * 4 + q + 1]};
-              const ActCore2 c = panel_act_core2(tv);
+              const ActCore2 c = act_core2_pkclamp(tv);
               const f32x2 s = kLn2 * c.mxt + c.dl;
               const f32x2 dg = gzc * (c.r - c.r * c.r) + gza * c.dl;
               const f32x2 z = raw * dg;
@@ -1868,8 +1658,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         c += __shfl_xor(c, 32, 64);
         if (lane < 32) s_col[rb * W + cbase + j * 32 + lane] = c;
       }
-      sa_all += panel_wave_sum(inv_sw * ((sa2.x + sa2.y) - 2.f * (sacc.x + sacc.y)));
-      sg_all += panel_wave_sum((kLn2 / gl) * (sg2.x + sg2.y));
+      sa_all += wave_sum_dpp(inv_sw * ((sa2.x + sa2.y) - 2.f * (sacc.x + sacc.y)));
+      sg_all += wave_sum_dpp((kLn2 / gl) * (sg2.x + sg2.y));
       if (hc == CH - 1 && lane == 0) {
         s_sc[32 + wave * 2] = sa_all;
         s_sc[33 + wave * 2] = sg_all;
@@ -1896,7 +1686,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
 
   // =============================== dH1 = dZ1 K1^T ============================================
   BNF_MARK(a, 9);
-  if (!BNF_PANEL_ZPEEL) zero_acc();
   if constexpr (c8)
     contract_all8(a.Wb8[1] + (int64_t)e * a.w8_batch, std::integral_constant<bool, F0>{}, std::true_type{});
   else
@@ -1935,7 +1724,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         (void)kDummy;
         const int t = 2 * i + j;
         f32x16& a0 = a0b[t & 1];
-        fair_prio(t);
         if constexpr (H0L) {   // the next tile's MFMA chain runs under this tile's epilogue
           if (t + 1 < 2 * RT) l0_tile(L, a0b[(t + 1) & 1], (t + 1) >> 1, (t + 1) & 1);
         } else {
@@ -1959,7 +1747,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
               const f32x2 tv = {a0[rg * 4 + q], a0[rg * 4 + q + 1]};
               f32x2 z = raw;
               if (!BNF_ABL(a, 2)) {
-                const ActCore2 c = panel_act_core2(tv);
+                const ActCore2 c = act_core2_pkclamp(tv);
                 const f32x2 s = kLn2 * c.mxt + c.dl;
                 const f32x2 dg = gzc * (c.r - c.r * c.r) + gza * c.dl;
                 z = raw * dg;
@@ -1973,7 +1761,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
             asm volatile("" : "+v"(sa2), "+v"(sg2), "+v"(sacc));
             if (BNF_EPI_FENCE_EVERY == 1 || (rg & 1)) __builtin_amdgcn_sched_barrier(0);
           }
-          if (j == 0 && i > 0 && !(BNF_PANEL_DK0 && a.dk0_fused)) block_to_global(L, a.dZ[0], i - 1, cbase);
+          if (j == 0 && i > 0) block_to_global(L, a.dZ[0], i - 1, cbase);
           continue;
         }
         const int lc = cbase + j * 32 + frow;
@@ -1986,7 +1774,7 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
             const f32x2 tv = f32x2{a0[rg * 4 + q], a0[rg * 4 + q + 1]} * gs0 + gb0[j];
             f32x2 z = raw;
             if (!BNF_ABL(a, 2)) {
-              const ActCore2 c = panel_act_core2(tv);
+              const ActCore2 c = act_core2_pkclamp(tv);
               const f32x2 s = kLn2 * c.mxt + c.dl;
               const f32x2 dg = gzc * (c.r - c.r * c.r) + gza * c.dl;
               z = raw * dg;
@@ -2000,11 +1788,10 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
           asm volatile("" : "+v"(sa2), "+v"(sg2), "+v"(sacc), "+v"(cs2[0]), "+v"(cs2[1]));
           if (BNF_EPI_FENCE_EVERY == 1 || (rg & 1)) __builtin_amdgcn_sched_barrier(0);
         }
-        if (j == 0 && i > 0 && !(BNF_PANEL_DK0 && a.dk0_fused)) block_to_global(L, a.dZ[0], i - 1, cbase);   // (deferred: see the layer-0 forward)
+        if (j == 0 && i > 0) block_to_global(L, a.dZ[0], i - 1, cbase);   // (deferred: see the layer-0 forward)
       }
     }
-    fair_prio_end();
-    if (!(BNF_PANEL_DK0 && a.dk0_fused)) block_to_global(L, a.dZ[0], RT - 1, cbase);
+    block_to_global(L, a.dZ[0], RT - 1, cbase);
     BNF_MARK(a, 11);
     if constexpr (!F0) {
 #pragma unroll
@@ -2014,8 +1801,8 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
         if (lane < 32) s_col[rb * W + cbase + j * 32 + lane] = c;
       }
     }
-    sa0_all += panel_wave_sum(inv_sw * ((sa2.x + sa2.y) - 2.f * (sacc.x + sacc.y)));
-    sg0_all += panel_wave_sum((kLn2 / gamma0) * (sg2.x + sg2.y));
+    sa0_all += wave_sum_dpp(inv_sw * ((sa2.x + sa2.y) - 2.f * (sacc.x + sacc.y)));
+    sg0_all += wave_sum_dpp((kLn2 / gamma0) * (sg2.x + sg2.y));
     if (hc == CH - 1 && lane == 0) {
       s_sc[32 + wave * 2] = sa0_all;
       s_sc[33 + wave * 2] = sg0_all;
@@ -2129,65 +1916,6 @@ __global__ __launch_bounds__(512, (WN == 8 && RT * CH == 2) ? 4 : 2) void k_pane
                (c0[rg * 4 + 2] + c1[rg * 4 + 2]) * inv_sf, (c0[rg * 4 + 3] + c1[rg * 4 + 3]) * inv_sf);
     }
   }
-#if BNF_PANEL_DK0
-  // ---- experiment: dK_0[f][c] += sum_r H0[r][f] dZ0[r][c] / sqrt F for this wave's 64 columns (both panels in LDS) ----
-  // 2 x 2 MFMA tiles (features x columns), K = the panel's BM rows; fragments by ds_read_b64_tr_b16 as in gemm_tn
-  // (within a 16-lane group lane i receives element i % 4 of the 8-byte datum addressed by lane 4 j + i / 4).
-  if constexpr (H0L && CH == 1 && FP == 64 && RB == 1) {
-    if (a.dk0_fused) {
-      const int lane = opaque_lane(tid) & 63;
-      const int kg = lane >> 5, frow = lane & 31, p = lane & 15, half = (lane >> 4) & 1;
-      const int prow = p >> 2, pcol = half * 16 + (p & 3) * 4;
-      const int cbase = slab(0) * 64;
-      typedef __attribute__((address_space(3))) char lds_char_t;
-      const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_t*)smem;
-      const uint32_t h0o = lds0 + (uint32_t)(h0s - smem);
-      f32x16 dk[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dk[i][j][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < BM / 16; ++ks) {
-        u32x2_t ra[2][2], rb[2][2];   // [t][tile]
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int row = ks * 16 + kg * 8 + t * 4 + prow;
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            ra[t][i] = lds_tr16_b64<0>(h0o + (uint32_t)(row * kH0Pitch + (i * 32 + pcol) * 2));
-            rb[t][i] = lds_tr16_b64<0>(lds0 + (uint32_t)(row * kPitchB + (cbase + i * 32 + pcol) * 2));
-          }
-        }
-        lds_tr_fence(ra, rb);
-        bf16x8 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const u32x4 wa = {ra[0][i].x, ra[0][i].y, ra[1][i].x, ra[1][i].y};
-          const u32x4 wb = {rb[0][i].x, rb[0][i].y, rb[1][i].x, rb[1][i].y};
-          fa[i] = __builtin_bit_cast(bf16x8, wa);
-          fb[i] = __builtin_bit_cast(bf16x8, wb);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) dk[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], dk[i][j], 0, 0, 0);
-      }
-      float* out = gr + a.off_k0;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int f = i * 32 + 8 * (r >> 2) + 4 * kg + (r & 3);
-            if (f < a.F) atomicAdd(&out[(int64_t)f * W + cbase + j * 32 + frow], dk[i][j][r] * inv_sf);
-          }
-    }
-  }
-#endif
   BNF_MARK(a, 13);
   if constexpr (H0L) {
     if (a.fbmeta) {
