@@ -32,6 +32,7 @@
 #include "bnf_kernels.h"
 #include "bnf_panel.h"
 #include "bnf_gemm8.h"
+#include "bnf_sampling.h"
 
 using namespace bnf;
 
@@ -1365,6 +1366,28 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
+// posterior-predictive sampling launches (bnf_sampling.h), one instantiation per observation model
+template <int OBS>
+static void launch_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, int64_t S,
+                                      uint64_t seed, int64_t row0, int64_t sample0, float* out) {
+  const int64_t gx = cdiv(R, 256 * kPredRowsPerThread);
+  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));
+  hipLaunchKernelGGL((k_predictive_samples<OBS>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
+                     (int32_t)M, R, S, seed, row0, sample0, out);
+}
+
+template <int OBS>
+static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
+                                         const int32_t* seg_offsets, const int32_t* seg_rows, int64_t G, int64_t S,
+                                         uint64_t seed, int64_t row0, int64_t sample0, double* partial, double* out) {
+  const int64_t nt = cdiv(R, kPredTile);
+  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
+  hipLaunchKernelGGL((k_predictive_group_sums<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
+                     (int32_t)M, R, seg_offsets, seg_rows, (int32_t)G, S, seed, row0, sample0, partial, out);
+  hipLaunchKernelGGL(k_predictive_group_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
+                     seg_offsets, (int32_t)G, R, S, partial, out);
+}
+
 extern "C" {
 
 int bnf_abi_version(void) { return BNF_ABI_VERSION; }
@@ -1924,6 +1947,58 @@ int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* au
   return BNF_OK;
 }
 
+
+// ---- posterior-predictive sampling (bnf_sampling.h) -----------------------------
+static int predictive_args(const bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           int64_t n_samples, int64_t row0, int64_t sample0) {
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!loc || !aux || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL || n_samples < 1)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (row0 < 0 || row0 + n_rows > (1LL << 56)) return fail(BNF_ERR_INVALID, "row0 + n_rows exceeds 2^56");
+  if (sample0 < 0 || sample0 + n_samples > (1LL << 32)) return fail(BNF_ERR_INVALID, "sample0 + n_samples exceeds 2^32");
+  return BNF_OK;
+}
+
+int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, float* out) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!out) return fail(BNF_ERR_INVALID, "argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  switch (h->cfg.obs_model) {
+    case BNF_OBS_NORMAL: launch_predictive_samples<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
+    case BNF_OBS_NB: launch_predictive_samples<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
+    default: launch_predictive_samples<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                              const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                              uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || !work || !out || n_groups < 1 || n_groups > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  const int64_t nt = cdiv(n_rows, kPredTile);
+  const size_t per_sample = (size_t)nt * 2 * sizeof(double);
+  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
+  if (chunk < 1)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
+                (long long)n_rows, per_sample);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemsetAsync(out, 0, (size_t)n_samples * (size_t)n_groups * sizeof(double), h->stream));   // empty groups
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
+    const int64_t n = std::min(chunk, n_samples - s0);
+    double* o = out + s0 * n_groups;
+    switch (h->cfg.obs_model) {
+      case BNF_OBS_NORMAL: launch_predictive_group_sums<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
+      case BNF_OBS_NB: launch_predictive_group_sums<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
+      default: launch_predictive_group_sums<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
 
 // ---- debug / introspection ---------------------------------------------------
 int bnf_debug_loss_and_grad(bnf_handle* h, int64_t epoch, int64_t step, float* grads, float* loss) {

@@ -602,7 +602,9 @@ enum : uint32_t {
   STREAM_SHUFFLE = 2,  // per-member per-epoch row shuffle (MAP)
   STREAM_VI_EPS = 3,   // reparameterisation noise
   STREAM_VI_BATCH = 4, // shared random batch of a VI step
-  STREAM_VI_DRAW = 5   // posterior draws after fitting
+  STREAM_VI_DRAW = 5,  // posterior draws after fitting
+  STREAM_PRED_COMPONENT = 6,  // mixture component of a posterior-predictive sample path (bnf_sampling.h)
+  STREAM_PRED_DRAW = 7        // observation noise of a sample path at one row (bnf_sampling.h)
 };
 
 __device__ __forceinline__ float u01_open(uint32_t x) {  // (0,1), 24 bits

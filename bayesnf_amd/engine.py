@@ -260,6 +260,48 @@ class Engine:
         _ptr(means), _ptr(out)), 'bnf_count_mixture_quantiles')
     return means, out
 
+  def predictive_samples(self, loc: torch.Tensor, aux: torch.Tensor, n_samples: int, seed, row0=0,
+                         sample0=0) -> torch.Tensor:
+    """Posterior-predictive sample paths (include/bnf.h bnf_predictive_samples): loc (M, R), aux (M, 3) as `forward`
+    returns them -> (n_samples, R) f32 on the device.  Path s draws one member for all rows, then every row from that
+    member's observation model.  row0 / sample0: global index of loc's first column / of the first path -- the values
+    are a pure function of (seed, path, global row), so chunks of any size reproduce the one big call."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    out = torch.empty((int(n_samples), R), dtype=torch.float32, device=self.device)
+    _native.check(self.lib.bnf_predictive_samples(
+        self.handle, _ptr(loc), _ptr(aux), M, R, int(n_samples), C.c_uint64(_native.seed_to_u64(seed)), int(row0),
+        int(sample0), _ptr(out)), 'bnf_predictive_samples')
+    return out
+
+  def predictive_group_sums(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
+                            row0=0, sample0=0) -> torch.Tensor:
+    """Totals of the same sample paths over groups of rows (include/bnf.h bnf_predictive_group_sums) -> (n_samples, G)
+    f64 on the device, without materialising the draws.  The rows come sorted by group as CSR: seg_offsets (G + 1),
+    seg_rows (R) int32 (`inference.csr_from_codes`).  Deterministic: the same call gives the same bits."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+                        ).to(self.device, dtype=torch.int32).contiguous()
+    off, rows = as_i32(seg_offsets), as_i32(seg_rows)
+    G = off.numel() - 1
+    if G < 1 or rows.numel() != R:
+      raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
+    n_samples = int(n_samples)
+    out = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+    # per-tile partial sums: 16 bytes per tile and path, at most ~64 MB (the library makes several passes beyond that)
+    per_path = 2 * (-(-R // _native.GROUP_TILE))
+    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // (8 * per_path))), dtype=torch.float64,
+                       device=self.device)
+    _native.check(self.lib.bnf_predictive_group_sums(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(work), C.c_size_t(work.numel() * 8),
+        _ptr(out)), 'bnf_predictive_group_sums')
+    torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

@@ -304,6 +304,65 @@ def predict_bnf(features, observation_model, params, model_args, quantiles,
   return means_np, [q_np[i] for i in range(q_np.shape[0])]
 
 
+# ---------------------------------------------------------------------------
+# posterior-predictive sample paths
+# ---------------------------------------------------------------------------
+_SAMPLE_CHUNK_CELLS = 1 << 26     # cells (sample x row, f32) of the device buffer one row chunk of sample_predictive fills
+
+
+def csr_from_codes(codes, n_groups):
+  """Rows sorted by group as CSR: integer group codes (R,) in [0, n_groups) -> (seg_offsets (n_groups + 1,) int32,
+  seg_rows (R,) int32); group g owns seg_rows[seg_offsets[g]:seg_offsets[g + 1]], rows ascending inside a group,
+  a code nobody carries is an empty segment.  The layout `bnf_predictive_group_sums` takes (include/bnf.h)."""
+  codes = np.asarray(codes)
+  if codes.ndim != 1 or (codes.size and not np.issubdtype(codes.dtype, np.integer)):
+    raise ValueError('group codes must be a 1-d integer array')
+  n_groups = int(n_groups)
+  if n_groups < 1 or codes.size == 0 or codes.size >= 2**31:
+    raise ValueError('need at least one group and between 1 and 2^31 - 1 rows')
+  if codes.min() < 0 or codes.max() >= n_groups:
+    raise ValueError(f'group codes must lie in [0, {n_groups})')
+  seg_offsets = np.zeros(n_groups + 1, dtype=np.int64)
+  np.cumsum(np.bincount(codes, minlength=n_groups), out=seg_offsets[1:])
+  seg_rows = np.argsort(codes, kind='stable')
+  return seg_offsets.astype(np.int32), seg_rows.astype(np.int32)
+
+
+def sample_predictive(features, observation_model, params, model_args, num_samples, seed, ensemble_dims,
+                      groups=None, compute_dtype=None):
+  """Joint posterior-predictive draws on the GPU (include/bnf.h bnf_predictive_samples / bnf_predictive_group_sums;
+  the reference draws with `.sample()` on its `likelihood_model()`).  Every leading ensemble dim of `params` --
+  devices, members, and for VI the posterior draws -- flattens to the M equally weighted mixture components, exactly
+  as in predict_bnf.  Sample path s uses ONE component for all rows, with observation noise per row on top.
+    groups=None                      -> (num_samples, n_rows) float32
+    groups=(seg_offsets, seg_rows)   -> (num_samples, G) float64 totals per group (`csr_from_codes`), summed on the
+                                        device without materialising the draws
+  The rows are drawn in chunks of _SAMPLE_CHUNK_CELLS // num_samples so that the device buffer stays bounded; the
+  values do not depend on the chunking (counter-based generator keyed by seed, path and global row)."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  seed64 = _native.seed_to_u64(seed)
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  loc = loc_all.reshape(-1, n_rows)
+  aux = aux_all.reshape(-1, 3)
+  try:
+    if groups is not None:
+      seg_offsets, seg_rows = groups
+      return eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64).cpu().numpy()
+    out = np.empty((num_samples, n_rows), dtype=np.float32)
+    chunk = max(1, _SAMPLE_CHUNK_CELLS // num_samples)
+    for r0 in range(0, n_rows, chunk):
+      r1 = min(n_rows, r0 + chunk)
+      out[:, r0:r1] = eng.predictive_samples(loc[:, r0:r1], aux, num_samples, seed64, row0=r0).cpu().numpy()
+    return out
+  finally:
+    eng.close()
+
+
 def _quantile_engine(net, obs, compute_dtype):
   """Forward-only handle that owns the quantile kernels (bnf_*_mixture_quantiles)."""
   return Engine(net, mode='map', members=1, forward_only=True, row_capacity=128, compute_dtype=compute_dtype)
@@ -354,6 +413,8 @@ class EnsembleLikelihood:
     return res[0] if np.ndim(q) == 0 else res
 
   def sample(self, seed=0):
+    """One draw per member, on the host (numpy).  Joint draws of the mixture -- any number of sample paths, or their
+    totals over groups of rows -- come from the GPU: `BayesianNeuralFieldEstimator.predict_samples`."""
     rng = np.random.default_rng(_native.seed_to_u64(seed))
     return self.loc + self.scale * rng.standard_normal(self.loc.shape)
 
@@ -423,6 +484,8 @@ class CountEnsembleLikelihood:
     return res[0] if np.ndim(q) == 0 else res
 
   def sample(self, seed=0):
+    """One draw per member, on the host (numpy).  Joint draws of the mixture -- any number of sample paths, or their
+    totals over groups of rows -- come from the GPU: `BayesianNeuralFieldEstimator.predict_samples`."""
     rng = np.random.default_rng(_native.seed_to_u64(seed))
     shape = np.broadcast_shapes(self.total_count.shape, self.logits.shape)
     # NB(tc, p) as a Gamma-Poisson mixture: rate ~ Gamma(tc, scale = e^logits)

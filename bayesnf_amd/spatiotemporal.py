@@ -179,6 +179,25 @@ class SpatiotemporalDataHandler:
     return scales
 
 
+def group_rows(table, group_by):
+  """Rows of `table` grouped by one column or a list of columns -> (keys, seg_offsets, seg_rows): `keys` the sorted
+  pandas Index (a MultiIndex for several columns) of the groups that occur, and the rows sorted by group as CSR
+  (`inference.csr_from_codes`): group keys[g] owns seg_rows[seg_offsets[g]:seg_offsets[g + 1]]."""
+  cols = [group_by] if isinstance(group_by, str) or not isinstance(group_by, (list, tuple)) else list(group_by)
+  missing = [c for c in cols if c not in table.columns]
+  if not cols or missing:
+    raise ValueError(f'group_by: {missing or "no column"} not among the columns of the table')
+  if len(table) == 0:
+    raise ValueError('group_by on an empty table')
+  index = pd.Index(table[cols[0]]) if len(cols) == 1 else pd.MultiIndex.from_frame(table[cols])
+  codes, keys = index.factorize(sort=True)
+  keys = keys.set_names(cols)
+  if (codes < 0).any():
+    raise ValueError('group_by columns hold missing values')
+  seg_offsets, seg_rows = inference.csr_from_codes(codes.astype(np.int64), len(keys))
+  return keys, seg_offsets, seg_rows
+
+
 # ---------------------------------------------------------------------------
 # estimators
 # ---------------------------------------------------------------------------
@@ -331,6 +350,29 @@ class BayesianNeuralFieldEstimator:
         approximate_quantiles=approximate_quantiles,
         compute_dtype=self.compute_dtype,
     )
+
+  def predict_samples(self, table, num_samples=1000, seed=0, group_by=None):
+    """Joint posterior-predictive sample paths at the rows of `table`, drawn on the GPU.  Each path uses one member
+    (VI: one member and one posterior draw) for all rows and adds that member's observation noise per row, so sums
+    over rows carry the right spread -- what no marginal quantile of `predict` gives.
+      group_by=None                    -> (num_samples, len(table)) float32
+      group_by=column or [columns]     -> (totals, keys): totals (num_samples, G) float64, the paths summed over
+        the rows of every group; keys the sorted pandas Index (MultiIndex for several columns) of the groups.  The
+        group columns are any columns of `table`, feature or not.
+    The same (seed, table) gives the same numbers whatever num_samples is asked for (path s does not change)."""
+    if self.params_ is None:
+      raise ValueError('predict_samples before fit')
+    if int(num_samples) < 1:
+      raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+    groups = keys = None
+    if group_by is not None:
+      keys, seg_offsets, seg_rows = group_rows(table, group_by)
+      groups = (seg_offsets, seg_rows)
+    rows = self.data_handler.get_test(table)
+    out = inference.sample_predictive(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype)
+    return out if group_by is None else (out, keys)
 
   def likelihood_model(self, table):
     """Predictive distribution of every member at the rows of `table`

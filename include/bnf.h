@@ -272,6 +272,41 @@ int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* au
                                 int64_t n_members, int64_t n_rows, const float* q,
                                 int32_t n_q, float* means, float* out);
 
+/* Posterior-predictive SAMPLE PATHS of the equal-weight mixture over members: what the reference draws with
+ * `.sample()` on the TFP distribution its `likelihood_model()` returns (spatiotemporal.py:433-468; models.py:160-191
+ * tfd.Normal / NegativeBinomial / ZeroInflatedNegativeBinomial), here as JOINT draws: sample path s picks ONE member
+ * c_s = floor(u n_members) for all rows, then draws every row independently from that member's distribution
+ * (observation model of the handle; NORMAL N(loc, aux[0]); NB total_count = 1 / aux[1], logits = -log aux[1] -
+ * log softplus(loc), drawn as Poisson(Gamma(total_count, scale e^logits)); ZINB: 0 with probability aux[2]).
+ *   loc DEVICE (n_members, n_rows) and aux DEVICE (n_members, 3) as written by bnf_forward
+ *   out DEVICE (n_samples, n_rows) f32 (counts above 2^24 rounded to the nearest float)
+ *   row0, sample0: global index of loc's first column / of out's first row.  The value at (sample s, row r) is a pure
+ *     function of (seed, sample0 + s, row0 + r, loc[c_s, r], aux[c_s]): a caller may cut rows and samples into chunks of
+ *     any size and gets the bits of the one big call.  row0 + n_rows <= 2^56, sample0 + n_samples <= 2^32.
+ * Counter layout (Philox4x32-10, key = seed; stream ids of their own beside the training streams, bnf_device.h):
+ *   member of path s:  (s, 0, 0, STREAM_PRED_COMPONENT), word 0
+ *   draw at (s, r):    (r bits 0..31, s, slot << 16 | trial, STREAM_PRED_DRAW | r bits 32..55 << 8); slot 0 the Normal
+ *     draw and the zero-inflation uniform, slot 1 the Gamma proposals (Marsaglia-Tsang), slot 2 the Poisson uniforms
+ *     (inversion below rate 10, PTRS above); every rejection loop stops after 64 proposals (bnf_sampling.h).
+ * Runs on the handle's stream, does not touch the training state. */
+int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, float* out);
+
+/* Totals of the same sample paths over groups of rows, without materialising the draws: out[s][g] = the f64 sum over
+ * the rows of group g of the f32 values bnf_predictive_samples writes for (seed, sample0 + s, row0 + r).  The reference
+ * has no counterpart (it would sum `.sample()` on the host).  Deterministic: no floating-point atomics, the order of
+ * every sum depends only on the grouping -- two calls give the same bits, counts are exact below 2^53.
+ *   seg_offsets DEVICE int32 (n_groups + 1), seg_rows DEVICE int32 (n_rows): the rows sorted by group as CSR; group g
+ *     owns seg_rows[seg_offsets[g] .. seg_offsets[g + 1]), [0] = 0, [n_groups] = n_rows, every row once (empty groups
+ *     allowed: total 0).  Entries of seg_rows outside [0, n_rows) add nothing.
+ *   work DEVICE, work_bytes: per-tile partial sums, 16 bytes x ceil(n_rows / BNF_GROUP_TILE) per sample path; the
+ *     samples are processed in as many passes as the buffer asks for (BNF_ERR_INVALID below one path's worth)
+ *   out DEVICE (n_samples, n_groups) f64 */
+#define BNF_GROUP_TILE 1024
+int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                              const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                              uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
