@@ -266,10 +266,42 @@ __device__ __forceinline__ float log_sigmoidf(float x) { return -softplusf(-x); 
 //   dout    d loss / d out            with loss = -c * ll
 //   d_par   d loss / d theta_par      par = log_noise_scale (NORMAL) or shape (NB / ZINB)
 //   d_infl  d loss / d inflated_loc_probs (ZINB)
+//
+// NB / ZINB.  mean = softplus(out), shape = softplus(theta_shape), tc = total_count = 1 / shape,
+// logits = -log shape - log mean, and TFP 0.24's log_prob is
+//   tc logsig(-logits) + y logsig(logits) + lgamma(tc + y) - lgamma(1 + y) - lgamma(tc).
+// Evaluated term by term in f32 that holds the fp32 gates only while the counts are small: 1 - sigmoid(logits) loses
+// all its digits once the NB mean mu = tc e^logits is >> tc, the lgamma triple cancels terms of size y log y, and
+// logsig(-logits) + digamma(tc + y) - digamma(tc) cancels to (y - mu) / tc when tc is large.  The same functions are
+// evaluated here in forms whose terms are of the size of the result (tests/epilogue_f32.py restates both in float32 and
+// tests/test_epilogue_f32.py compares them: <= 3e-6 of the sum of the rows' magnitudes for total_count 0.025 .. 2e3 and
+// means 0.01 .. 2e6, where the verbatim forms reach 0.8).  With sm = shape mean = e^-logits, rsm = 1 / sm, mu = tc rsm:
+//   d lp / d logits = y (1 - sg) - tc sg = (y - mu) / (1 + rsm)            one subtraction of two computed numbers
+//   logsig(-logits) = -log1p(rsm),  logsig(logits) = -log1p(sm)            no round trip through log and exp
+//   L1 = log((tc + y) / (tc + mu))                                         log1p((y - mu) / (tc + mu)) near 1
+//   lp, y an integer < 10:  -tc log1p(rsm) + sum_{j < y} log((tc + j) / (1 + j) / (1 + sm))     (lgamma recurrence)
+//   lp, y >= 10 (Stirling's series for lgamma(tc + y) and lgamma(1 + y), the terms of size y log y taken out by hand):
+//        tc L1 + y L2 - log((tc + y) y) / 2 + A(tc) + corr(tc + y) - corr(y),   corr(x) = 1 / (12 x) - 1 / (360 x^3),
+//        L2 = log((tc + y) mu / (y (tc + mu))) = log1p(tc (mu - y) / (y (tc + mu))),
+//        A(tc) = tc log tc - tc - lgamma(tc)  ( = log(tc / (2 pi)) / 2 - corr(tc) for tc >= 10)
+//   d lp / d tc, tc + y >= 6:  [log tc - digamma(tc)] + L1 - 1 / (2 (tc + y)) - tail(tc + y)    (digammaf's series;
+//        the bracket is 1 / (2 tc) + tail(tc) for tc >= 6);  tc + y < 6, y an integer:  -log1p(rsm) + sum_{j < y} 1 / (tc + j)
+// A y that is no integer (no count, but the ABI takes any float) and is below the thresholds takes TFP's form.
 // ---------------------------------------------------------------------------
 struct RowLoss {
   float ll, dout, d_par, d_infl;
 };
+
+// x >= 6: digamma(x) = log x - 1 / (2 x) - digamma_tail(x)
+__device__ __forceinline__ float digamma_tail(float x) {
+  const float r = 1.0f / x, r2 = r * r;
+  return r2 * (1.f / 12.f - r2 * (1.f / 120.f - r2 * (1.f / 252.f - r2 * (1.f / 240.f))));
+}
+// x >= 10: lgamma(x + 1) = x log x - x + log(2 pi x) / 2 + stirling_corr(x)   (next term 1 / (1260 x^5) < 1e-8)
+__device__ __forceinline__ float stirling_corr(float x) {
+  const float ix = 1.0f / x;
+  return ix * (1.f / 12.f) * (1.f - ix * ix * (1.f / 30.f));
+}
 
 __device__ __forceinline__ RowLoss row_loss_eval(int obs, const float* __restrict__ th, int off_lns,
                                                  int off_shape, int off_infl, float yv, float out,
@@ -287,19 +319,46 @@ __device__ __forceinline__ RowLoss row_loss_eval(int obs, const float* __restric
     o.d_par = -c * (res * res / (sigma * sigma * sigma) - 1.0f / sigma) * expf(lns);
     return o;
   }
-  // NB / ZINB: mean = softplus(out), shape = softplus(theta_shape), total_count = 1/shape,
-  // logits = -log shape - log mean;  TFP 0.24 log_prob:
-  //   tc logsig(-logits) + y logsig(logits) + lgamma(tc+y) - lgamma(1+y) - lgamma(tc)
   const float ths = th[off_shape];
   const float shape = softplusf(ths);
   const float tc = 1.0f / shape;
   const float mean = softplusf(out);
-  const float logits = -logf(shape) - logf(mean);
-  const float sg = sigmoidf(logits);
-  const float lsn = log_sigmoidf(-logits);
-  float lp = tc * lsn + yv * log_sigmoidf(logits) + lgammaf(tc + yv) - lgammaf(1.0f + yv) - lgammaf(tc);
-  float dl_dlogits = yv * (1.0f - sg) - tc * sg;
-  float dl_dtc = lsn + digammaf(tc + yv) - digammaf(tc);
+  const float sm = shape * mean;              // e^-logits
+  const float rsm = 1.0f / sm;                // e^logits
+  const float mu = tc * rsm;                  // the NB mean
+  const float lsn = -log1pf(rsm);             // log sigmoid(-logits)
+  float dl_dlogits = (yv - mu) * (1.0f / (1.0f + rsm));
+  const float n = tc + yv, den = tc + mu, delta = yv - mu;
+  const float l1 = fabsf(delta) <= 0.5f * den ? log1pf(delta / den) : logf(n / den);
+  const bool integer = yv == floorf(yv);
+  float lp;
+  if (yv >= 10.f) {
+    const float x2 = tc * (mu - yv) / (yv * den);
+    const float l2 = fabsf(x2) <= 0.5f ? log1pf(x2) : logf((n / den) * (mu / yv));
+    const float a_tc = tc >= 10.f ? 0.5f * logf(tc) - 0.918938533204672742f - stirling_corr(tc)
+                                  : tc * logf(tc) - tc - lgammaf(tc);
+    lp = tc * l1 + yv * l2 - 0.5f * (logf(n) + logf(yv)) + a_tc + stirling_corr(n) - stirling_corr(yv);
+  } else if (integer) {
+    const float sgp = 1.0f / (1.0f + sm);     // sigmoid(logits)
+    float acc = 0.f;
+#pragma unroll 1
+    for (float j = 0.f; j < yv; j += 1.0f) acc += logf((tc + j) / (1.0f + j) * sgp);
+    lp = tc * lsn + acc;
+  } else {
+    lp = tc * lsn - yv * log1pf(sm) + lgammaf(n) - lgammaf(1.0f + yv) - lgammaf(tc);
+  }
+  float dl_dtc;
+  if (n >= 6.f) {
+    const float g_tc = tc >= 6.f ? 0.5f / tc + digamma_tail(tc) : logf(tc) - digammaf(tc);
+    dl_dtc = g_tc + l1 - 0.5f / n - digamma_tail(n);
+  } else if (integer) {
+    float hs = 0.f;
+#pragma unroll 1
+    for (float j = 0.f; j < fminf(yv, 6.f); j += 1.0f) hs += 1.0f / (tc + j);   // (the bound: tc + y < 6 unless tc is a NaN)
+    dl_dtc = lsn + hs;
+  } else {
+    dl_dtc = lsn + digammaf(n) - digammaf(tc);
+  }
   if (obs == 2 /* BNF_OBS_ZINB */) {
     // Mixture(cat = [1 - pi, pi], [NB, delta_0])
     const float thp = th[off_infl];
@@ -307,10 +366,10 @@ __device__ __forceinline__ RowLoss row_loss_eval(int obs, const float* __restric
     float dlp_dpi;
     if (yv == 0.f) {
       const float p0 = expf(lp);
-      const float den = (1.0f - pi) * p0 + pi;
-      const float w = (1.0f - pi) * p0 / den;
-      dlp_dpi = (1.0f - p0) / den;
-      lp = logf(den);
+      const float den0 = (1.0f - pi) * p0 + pi;
+      const float w = (1.0f - pi) * p0 / den0;
+      dlp_dpi = (1.0f - p0) / den0;
+      lp = logf(den0);
       dl_dlogits *= w; dl_dtc *= w;
     } else {
       dlp_dpi = -1.0f / (1.0f - pi);

@@ -166,6 +166,14 @@ class Engine:
     t = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float32))
     self.params.copy_(t.reshape(-1).to(self.device))
 
+  def set_targets(self, y):
+    """New targets y (N,) for the rows bound at construction: overwrites the device copy in place (every step gathers
+    its batch's targets from it)."""
+    t = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float64), dtype=np.float32))
+    if self.y is None or t.shape != self.y.shape:
+      raise ValueError(f'targets must have shape {None if self.y is None else tuple(self.y.shape)}; got {tuple(t.shape)}')
+    self.y.copy_(t.to(self.device))
+
   def get_params(self) -> np.ndarray:
     p = self.params.detach().cpu().numpy()
     if self.mode == 'vi':

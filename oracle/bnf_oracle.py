@@ -314,9 +314,10 @@ def noise_scale(model, theta):
   return 0.01 + np.exp(model.view(theta, 'log_noise_scale'))
 
 
-def normal_loglik(out, y, sigma):
+def normal_loglik(out, y, sigma, per_row=False):
   r = (y - out) / sigma[:, None]
-  return np.sum(-0.5 * r * r - np.log(sigma)[:, None] - 0.5 * LOG_2PI, axis=-1)
+  ll = -0.5 * r * r - np.log(sigma)[:, None] - 0.5 * LOG_2PI
+  return ll if per_row else np.sum(ll, axis=-1)
 
 
 def log_prior(model, theta):
@@ -354,17 +355,20 @@ def zinb_log_prob(y, total_count, logits, pi):
   return np.where(y == 0, at0, np.log1p(-pi) + lp_nb)
 
 
-def loglik(model, theta, out, y):
+def loglik(model, theta, out, y, per_row=False):
+  """Sum over the rows (E,), or with per_row the rows' own terms (E,B)."""
   om = model.observation_model
   if om == 'NORMAL':
-    return normal_loglik(out, y, noise_scale(model, theta))
+    return normal_loglik(out, y, noise_scale(model, theta), per_row)
   tc, logits = nb_logits_total_count(model, theta, out)
   if om == 'NB':
-    return np.sum(nb_log_prob(y, tc, logits), axis=-1)
-  if om == 'ZINB':
+    ll = nb_log_prob(y, tc, logits)
+  elif om == 'ZINB':
     pi = sigmoid(model.view(theta, 'inflated_loc_probs'))[:, None]
-    return np.sum(zinb_log_prob(y, tc, logits, pi), axis=-1)
-  raise AssertionError(om)
+    ll = zinb_log_prob(y, tc, logits, pi)
+  else:
+    raise AssertionError(om)
+  return ll if per_row else np.sum(ll, axis=-1)
 
 
 # --------------------------------------------------------------------------
@@ -384,10 +388,15 @@ def map_loss(model, theta, x, y, n_total, prior_weight=1.0, dtype=np.float64,
   return -val
 
 
-def _dloglik_dout_and_params(model, theta, out, y):
-  """d loglik / d out (E,B) and direct grads wrt lns / shape / infl (E,)."""
+def _dloglik_dout_and_params(model, theta, out, y, per_row=False):
+  """d loglik / d out (E,B) and direct grads wrt lns / shape / infl (E,).
+
+  per_row: also the rows' own terms of the direct grads, {leaf name: (E,B)}
+  (their sums over the rows are the entries of the second result).
+  """
   E = theta.shape[0]
   g_direct = np.zeros_like(theta)
+  rows = {}
   om = model.observation_model
   if om == 'NORMAL':
     lns = model.view(theta, 'log_noise_scale')
@@ -396,6 +405,10 @@ def _dloglik_dout_and_params(model, theta, out, y):
     dout = r / (sigma**2)[:, None]
     dsig = np.sum(r * r, axis=-1) / sigma**3 - y.shape[-1] / sigma
     g_direct[:, model.leaf['log_noise_scale'].offset] = dsig * np.exp(lns)
+    if per_row:
+      rows['log_noise_scale'] = (r * r / (sigma**3)[:, None] -
+                                 1.0 / sigma[:, None]) * np.exp(lns)[:, None]
+      return dout, g_direct, rows
     return dout, g_direct
   # NB / ZINB:  mean = softplus(out), shape = softplus(th_shape)
   th_shape = model.view(theta, 'shape')
@@ -419,14 +432,18 @@ def _dloglik_dout_and_params(model, theta, out, y):
                        -1.0 / (1.0 - pi))
     g_direct[:, model.leaf['inflated_loc_probs'].offset] = np.sum(
         dlp_dpi * (pi * (1 - pi)), axis=-1)
+    rows['inflated_loc_probs'] = dlp_dpi * (pi * (1 - pi))
     dl_dlogits = dl_dlogits * w
     dl_dtc = dl_dtc * w
   # logits = -log shape - log mean ; tc = 1/shape
   dmean = -dl_dlogits / mean
   dout = dmean * sigmoid(out)
-  dshape = np.sum(-dl_dlogits / shape[:, None] - dl_dtc / (shape**2)[:, None],
-                  axis=-1)
+  dshape_rows = -dl_dlogits / shape[:, None] - dl_dtc / (shape**2)[:, None]
+  dshape = np.sum(dshape_rows, axis=-1)
   g_direct[:, model.leaf['shape'].offset] = dshape * sigmoid(th_shape)
+  if per_row:
+    rows['shape'] = dshape_rows * sigmoid(th_shape)[:, None]
+    return dout, g_direct, rows
   return dout, g_direct
 
 
