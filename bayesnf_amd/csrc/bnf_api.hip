@@ -33,6 +33,7 @@
 #include "bnf_panel.h"
 #include "bnf_gemm8.h"
 #include "bnf_sampling.h"
+#include "bnf_scoring.h"
 
 using namespace bnf;
 
@@ -1388,6 +1389,29 @@ static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const 
                      seg_offsets, (int32_t)G, R, S, partial, out);
 }
 
+// held-out scoring launches (bnf_scoring.h), one instantiation per observation model
+template <int OBS>
+static void launch_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, const float* y,
+                                     double* ll_partial, double* pair_partial, int64_t n_slots, double* member_ll,
+                                     float* lpd, float* pit, float* crps) {
+  const int64_t nt = cdiv(R, kScoreTile);
+  if (member_ll) {
+    hipLaunchKernelGGL((k_score_member_ll<OBS>), dim3((unsigned)nt, (unsigned)std::min<int64_t>(M, 65535)), dim3(256), 0,
+                       h->stream, loc, aux, (int32_t)M, R, y, ll_partial);
+    hipLaunchKernelGGL(k_score_member_ll_combine, dim3(cdiv(M, 4)), dim3(256), 0, h->stream, ll_partial, (int32_t)M, nt,
+                       member_ll);
+  }
+  if (crps)
+    hipLaunchKernelGGL(k_score_crps_pairs, dim3((unsigned)nt, (unsigned)n_slots), dim3(256), 0, h->stream, loc, aux,
+                       (int32_t)M, R, pair_partial);
+  if (lpd || crps || (pit && OBS == BNF_OBS_NORMAL))
+    hipLaunchKernelGGL((k_score_rows<OBS>), dim3(cdiv(R, 64)), dim3(64), 0, h->stream, loc, aux, (int32_t)M, R, y,
+                       pair_partial, (int32_t)n_slots, lpd, pit, crps);
+  if (pit && OBS != BNF_OBS_NORMAL)
+    hipLaunchKernelGGL(k_score_count_pit, dim3(cdiv(R, 64), 2), dim3(64), 0, h->stream, loc, aux, (int32_t)M, R,
+                       (int32_t)OBS, y, pit);
+}
+
 extern "C" {
 
 int bnf_abi_version(void) { return BNF_ABI_VERSION; }
@@ -1995,6 +2019,36 @@ int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux,
       case BNF_OBS_NB: launch_predictive_group_sums<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
       default: launch_predictive_group_sums<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
     }
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- held-out scoring (bnf_scoring.h) ---------------------------------------------
+int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                          const float* y, void* work, size_t work_bytes, double* member_ll, float* lpd, float* pit,
+                          float* crps) {
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!loc || !aux || !y || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (crps && h->cfg.obs_model != BNF_OBS_NORMAL)
+    return fail(BNF_ERR_INVALID, "crps: closed form for the NORMAL observation model only");
+  const int64_t nt = cdiv(n_rows, kScoreTile);
+  const int64_t n_chunks = cdiv(n_members, kScoreChunk);
+  const int64_t n_slots = std::min<int64_t>((n_chunks + 1) / 2, kScoreMaxSlots);
+  const size_t ll_bytes = member_ll ? (size_t)n_members * (size_t)nt * sizeof(double) : 0;
+  const size_t pair_bytes = crps ? (size_t)n_rows * (size_t)n_slots * sizeof(double) : 0;
+  if (ll_bytes + pair_bytes > 0 && (!work || work_bytes < ll_bytes + pair_bytes))
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld members x %lld rows need %zu", work ? work_bytes : (size_t)0,
+                (long long)n_members, (long long)n_rows, ll_bytes + pair_bytes);
+  if (!member_ll && !lpd && !pit && !crps) return BNF_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  double* ll_partial = (double*)work;
+  double* pair_partial = (double*)((char*)work + ll_bytes);
+  switch (h->cfg.obs_model) {
+    case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+    case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+    default: launch_predictive_scores<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
   }
   HIPCHK(hipGetLastError());
   return BNF_OK;

@@ -310,6 +310,44 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
     return out
 
+  def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
+                        lpd=True, pit=True) -> dict:
+    """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),
+    aux (M, 3) as `forward` returns them -> dict of device tensors, one per output asked for:
+      'member_ll' (M,) f64   sum over the rows with a finite y of each member's log density
+      'lpd' (R,) f32         log density of the equal-weight mixture
+      'pit' (2, R) f32       mixture CDF at y and just below y
+      'crps' (R,) f32        NORMAL only (crps=None: exactly then; crps=True on a count handle is the library's error)
+    Rows whose y is NaN come back NaN and do not enter member_ll.  Deterministic: the same call gives the same bits."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    y = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
+         ).to(self.device, dtype=torch.float32).contiguous()
+    if y.shape != (R,):
+      raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
+    if crps is None:
+      crps = self.net.observation_model == 'NORMAL'
+    out = {}
+    if member_ll:
+      out['member_ll'] = torch.empty((M,), dtype=torch.float64, device=self.device)
+    if lpd:
+      out['lpd'] = torch.empty((R,), dtype=torch.float32, device=self.device)
+    if pit:
+      out['pit'] = torch.empty((2, R), dtype=torch.float32, device=self.device)
+    if crps:
+      out['crps'] = torch.empty((R,), dtype=torch.float32, device=self.device)
+    # partial sums (the formula of include/bnf.h): per member and row tile for member_ll, per row and slot for crps
+    n_chunks = -(-M // _native.SCORE_MEMBER_CHUNK)
+    n_work = ((M * (-(-R // _native.SCORE_ROW_TILE)) if member_ll else 0) +
+              (R * min((n_chunks + 1) // 2, _native.SCORE_MAX_SLOTS) if crps else 0))
+    work = torch.empty(max(1, n_work), dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_predictive_scores(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(work), C.c_size_t(n_work * 8), _ptr(out.get('member_ll')),
+        _ptr(out.get('lpd')), _ptr(out.get('pit')), _ptr(out.get('crps'))), 'bnf_predictive_scores')
+    torch.cuda.synchronize(self.device)     # `work` and the device copy of `y` are released on return
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

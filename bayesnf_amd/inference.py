@@ -363,6 +363,38 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
     eng.close()
 
 
+# ---------------------------------------------------------------------------
+# scores of held-out observations
+# ---------------------------------------------------------------------------
+def score_predictive(features, target, observation_model, params, model_args, ensemble_dims, compute_dtype=None):
+  """Held-out observations `target` (n_rows,) scored against the ensemble on the GPU (include/bnf.h
+  bnf_predictive_scores).  Every leading ensemble dim of `params` flattens to the M equally weighted mixture
+  components, exactly as in predict_bnf.  NaN targets are allowed: their rows come back NaN and do not enter the
+  per-member sums.  -> dict of numpy arrays:
+    'log_density' (n_rows,) float32      log density of the mixture at the target
+    'pit' (2, n_rows) float32            mixture CDF at the target and just below it (equal for NORMAL)
+    'crps' (n_rows,) float32             NORMAL only
+    'member_log_prob' lead dims, float64 every member's log density summed over the scored rows -- what
+                                         `likelihood_model(...).log_prob(target)` gives on the host"""
+  features = np.asarray(features, dtype=np.float64)
+  target = np.asarray(target, dtype=np.float64)
+  n_rows = features.shape[0]
+  if target.shape != (n_rows,):
+    raise ValueError(f'target must hold one observation per row ({n_rows},); got {target.shape}')
+  net, eng, lead, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    res = eng.predictive_scores(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3),
+                                np.ascontiguousarray(target, dtype=np.float32))
+    out = {'log_density': res['lpd'].cpu().numpy(), 'pit': res['pit'].cpu().numpy(),
+           'member_log_prob': res['member_ll'].cpu().numpy().reshape(tuple(lead))}
+    if 'crps' in res:
+      out['crps'] = res['crps'].cpu().numpy()
+    return out
+  finally:
+    eng.close()
+
+
 def _quantile_engine(net, obs, compute_dtype):
   """Forward-only handle that owns the quantile kernels (bnf_*_mixture_quantiles)."""
   return Engine(net, mode='map', members=1, forward_only=True, row_capacity=128, compute_dtype=compute_dtype)

@@ -374,6 +374,37 @@ class BayesianNeuralFieldEstimator:
         ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype)
     return out if group_by is None else (out, keys)
 
+  def score(self, table):
+    """The forecast at the rows of `table` scored against the observations `table[target_col]`, on the GPU.  NaN
+    targets are allowed: their rows are reported as NaN and left out of every sum and mean.  -> dict:
+      'n'                 number of rows scored (finite targets)
+      'log_density'       (len(table),) log density of the equal-weight mixture over members at the target
+      'pit'               (2, len(table)) mixture CDF at the target and just below it (equal for NORMAL; for counts a
+                          randomised PIT is uniform between the two)
+      'crps'              (len(table),) continuous ranked probability score; NORMAL only, absent otherwise
+      'member_log_prob'   leading ensemble dims of `params_`: every member's log density summed over the scored rows
+                          (`likelihood_model(table).log_prob(target)` without the trip through the host)
+      'mean_log_density', 'mean_crps' (NORMAL)   means over the scored rows"""
+    if self.params_ is None:
+      raise ValueError('score before fit')
+    if self.target_col not in table.columns:
+      raise ValueError(f'score: the target column {self.target_col!r} is not among the columns of the table')
+    y = np.asarray(table[self.target_col].values, dtype=np.float64)
+    if np.isinf(y).any():
+      raise ValueError('score: infinite targets')
+    seen = y[np.isfinite(y)]
+    if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
+      raise ValueError(f'score: the {self.observation_model} observation model takes non-negative integer targets')
+    rows = self.data_handler.get_test(table)
+    out = inference.score_predictive(
+        rows, y, self.observation_model, self.params_, self._model_args(rows.shape),
+        ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype)
+    out['n'] = int(seen.size)
+    for key in ('log_density', 'crps'):
+      if key in out:
+        out['mean_' + key] = float(np.mean(out[key][np.isfinite(y)], dtype=np.float64)) if seen.size else float('nan')
+    return out
+
   def likelihood_model(self, table):
     """Predictive distribution of every member at the rows of `table`
     (reference :433-468 returns a TFP Independent(Normal/NB/ZINB))."""

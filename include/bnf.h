@@ -307,6 +307,33 @@ int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux,
                               const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
                               uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out);
 
+/* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
+ * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
+ * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
+ * y DEVICE (n_rows,) f32.  Four outputs, each skipped when its pointer is NULL:
+ *   member_ll DEVICE (n_members,) f64: sum over the rows with a finite y of log p_m(y_r) -- the per-member `log_prob`,
+ *     evaluated in the forms of the training loss (bnf_scoring.h), so that held-out and training likelihood agree
+ *   lpd DEVICE (n_rows,) f32: log((1 / M) sum_m p_m(y_r)), formed in log space: finite where every p_m underflows
+ *   pit DEVICE (2, n_rows) f32: [0] = F(y_r), [1] = F(y_r-) of the mixture (NORMAL: equal; counts: F at the integer
+ *     below y_r, 0 at y_r = 0): a randomised PIT is uniform on [pit[1], pit[0]]
+ *   crps DEVICE (n_rows,) f32: NORMAL handles only (BNF_ERR_INVALID if non-NULL on a count handle), the closed form for
+ *     a Normal mixture, (1 / M) sum_i A(y - mu_i, s_i) - (1 / (2 M^2)) sum_ij A(mu_i - mu_j, sqrt(s_i^2 + s_j^2)),
+ *     A(m, s) = m (2 Phi(m / s) - 1) + 2 s phi(m / s)
+ * A row whose y is NaN or infinite gives NaN in every per-row output and adds nothing to member_ll.
+ * Every term is f32, every sum over members, pairs of members and rows f64 in an order the shapes fix: no floating-point
+ * atomics, two calls give the same bits.
+ *   work DEVICE, work_bytes: partial sums, needed for member_ll and crps only (may be NULL otherwise):
+ *       8 * n_members * ceil(n_rows / BNF_SCORE_ROW_TILE)                                             if member_ll
+ *     + 8 * n_rows * min(ceil(ceil(n_members / BNF_SCORE_MEMBER_CHUNK) / 2), BNF_SCORE_MAX_SLOTS)     if crps
+ *     bytes; BNF_ERR_INVALID below that, and for n_members < 1 or n_rows < 1.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+#define BNF_SCORE_ROW_TILE 1024
+#define BNF_SCORE_MEMBER_CHUNK 8
+#define BNF_SCORE_MAX_SLOTS 64
+int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                          const float* y, void* work, size_t work_bytes,
+                          double* member_ll, float* lpd, float* pit, float* crps);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
