@@ -34,6 +34,7 @@
 #include "bnf_gemm8.h"
 #include "bnf_sampling.h"
 #include "bnf_scoring.h"
+#include "bnf_rps.h"
 
 using namespace bnf;
 
@@ -1412,6 +1413,16 @@ static void launch_predictive_scores(bnf_handle* h, const float* loc, const floa
                        (int32_t)OBS, y, pit);
 }
 
+// ranked probability score (bnf_rps.h): one wave per row, the rows beyond 2^20 blocks by grid stride
+template <int OBS>
+static void launch_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, const float* y,
+                             float* rps) {
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_count_rps<OBS>, (int)rps_lds_bytes(BNF_RPS_MAX_MEMBERS), &attr_done);
+  hipLaunchKernelGGL((k_count_rps<OBS>), dim3((unsigned)std::min<int64_t>(R, 1 << 20)), dim3(64), rps_lds_bytes(M),
+                     h->stream, loc, aux, (int32_t)M, R, y, rps);
+}
+
 extern "C" {
 
 int bnf_abi_version(void) { return BNF_ABI_VERSION; }
@@ -2050,6 +2061,24 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
     case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
     default: launch_predictive_scores<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
   }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- ranked probability score of count forecasts (bnf_rps.h) -----------------------
+int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows, const float* y,
+                  float* rps) {
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!loc || !aux || !y || !rps || n_members < 1 || n_rows < 1 || n_rows > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (n_members > BNF_RPS_MAX_MEMBERS)
+    return fail(BNF_ERR_INVALID, "%lld members: the ranked probability score takes at most %d", (long long)n_members,
+                BNF_RPS_MAX_MEMBERS);
+  if (h->cfg.obs_model == BNF_OBS_NORMAL)
+    return fail(BNF_ERR_INVALID, "rps: count observation models only (NORMAL: the crps of bnf_predictive_scores)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->cfg.obs_model == BNF_OBS_NB) launch_count_rps<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, rps);
+  else launch_count_rps<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, rps);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -348,6 +348,23 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work` and the device copy of `y` are released on return
     return out
 
+  def count_rps(self, loc: torch.Tensor, aux: torch.Tensor, y) -> torch.Tensor:
+    """NB / ZINB: the ranked probability score -- the CRPS of a count forecast -- of the observations y (R,) against
+    the equal-weight mixture over members (include/bnf.h bnf_count_rps): loc (M, R), aux (M, 3) as `forward` returns
+    them -> (R,) f32 on the device.  NaN where y is NaN, negative or not an integer, and where the row's window is longer
+    than BNF_RPS_MAX_TERMS.  A NORMAL handle is the library's error (ValueError).  Deterministic."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    y = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
+         ).to(self.device, dtype=torch.float32).contiguous()
+    if y.shape != (R,):
+      raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
+    out = torch.empty((R,), dtype=torch.float32, device=self.device)
+    _native.check(self.lib.bnf_count_rps(self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(out)), 'bnf_count_rps')
+    torch.cuda.synchronize(self.device)     # the device copy of `y` is released on return
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

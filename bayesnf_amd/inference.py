@@ -366,7 +366,8 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
 # ---------------------------------------------------------------------------
 # scores of held-out observations
 # ---------------------------------------------------------------------------
-def score_predictive(features, target, observation_model, params, model_args, ensemble_dims, compute_dtype=None):
+def score_predictive(features, target, observation_model, params, model_args, ensemble_dims, compute_dtype=None,
+                     rps=False):
   """Held-out observations `target` (n_rows,) scored against the ensemble on the GPU (include/bnf.h
   bnf_predictive_scores).  Every leading ensemble dim of `params` flattens to the M equally weighted mixture
   components, exactly as in predict_bnf.  NaN targets are allowed: their rows come back NaN and do not enter the
@@ -375,7 +376,12 @@ def score_predictive(features, target, observation_model, params, model_args, en
     'pit' (2, n_rows) float32            mixture CDF at the target and just below it (equal for NORMAL)
     'crps' (n_rows,) float32             NORMAL only
     'member_log_prob' lead dims, float64 every member's log density summed over the scored rows -- what
-                                         `likelihood_model(...).log_prob(target)` gives on the host"""
+                                         `likelihood_model(...).log_prob(target)` gives on the host
+    'rps' (n_rows,) float32              with rps=True, NB / ZINB only: the ranked probability score (the CRPS of a count
+                                         forecast; include/bnf.h bnf_count_rps), NaN where the row's window is longer
+                                         than BNF_RPS_MAX_TERMS"""
+  if rps and observation_model == 'NORMAL':
+    raise ValueError("rps=True is for the count observation models (NB, ZINB); the NORMAL model's score is 'crps'")
   features = np.asarray(features, dtype=np.float64)
   target = np.asarray(target, dtype=np.float64)
   n_rows = features.shape[0]
@@ -384,12 +390,14 @@ def score_predictive(features, target, observation_model, params, model_args, en
   net, eng, lead, loc_all, aux_all = _ensemble_forecast(
       features, observation_model, params, model_args, ensemble_dims, compute_dtype)
   try:
-    res = eng.predictive_scores(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3),
-                                np.ascontiguousarray(target, dtype=np.float32))
+    loc, aux, y32 = loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), np.ascontiguousarray(target, dtype=np.float32)
+    res = eng.predictive_scores(loc, aux, y32)
     out = {'log_density': res['lpd'].cpu().numpy(), 'pit': res['pit'].cpu().numpy(),
            'member_log_prob': res['member_ll'].cpu().numpy().reshape(tuple(lead))}
     if 'crps' in res:
       out['crps'] = res['crps'].cpu().numpy()
+    if rps:
+      out['rps'] = eng.count_rps(loc, aux, y32).cpu().numpy()
     return out
   finally:
     eng.close()

@@ -374,9 +374,11 @@ class BayesianNeuralFieldEstimator:
         ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype)
     return out if group_by is None else (out, keys)
 
-  def score(self, table):
+  def score(self, table, rps=False):
     """The forecast at the rows of `table` scored against the observations `table[target_col]`, on the GPU.  NaN
-    targets are allowed: their rows are reported as NaN and left out of every sum and mean.  -> dict:
+    targets are allowed: their rows are reported as NaN and left out of every sum and mean.  rps=True (NB / ZINB;
+    ValueError on NORMAL, whose score of this kind is 'crps') adds the ranked probability score, the CRPS of a count
+    forecast: sum_k (F(k) - 1{k >= target})^2 with F the mixture CDF.  -> dict:
       'n'                 number of rows scored (finite targets)
       'log_density'       (len(table),) log density of the equal-weight mixture over members at the target
       'pit'               (2, len(table)) mixture CDF at the target and just below it (equal for NORMAL; for counts a
@@ -384,9 +386,16 @@ class BayesianNeuralFieldEstimator:
       'crps'              (len(table),) continuous ranked probability score; NORMAL only, absent otherwise
       'member_log_prob'   leading ensemble dims of `params_`: every member's log density summed over the scored rows
                           (`likelihood_model(table).log_prob(target)` without the trip through the host)
-      'mean_log_density', 'mean_crps' (NORMAL)   means over the scored rows"""
+      'mean_log_density', 'mean_crps' (NORMAL)   means over the scored rows
+      'rps'               rps=True: (len(table),) ranked probability score; NaN also on a row whose forecast is so wide
+                          that the sum would take more than 2^20 terms (a mean of 1e6 at total_count 0.05 is)
+      'mean_rps'          rps=True: mean over the scored rows whose 'rps' is not NaN
+      'rps_capped'        rps=True: the rows with a finite target whose 'rps' is NaN -- capped, or a member whose
+                          parameters are not finite (0 at any realistic count forecast)"""
     if self.params_ is None:
       raise ValueError('score before fit')
+    if rps and self.observation_model == 'NORMAL':
+      raise ValueError("score: rps=True is for the count observation models (NB, ZINB); NORMAL is scored by 'crps'")
     if self.target_col not in table.columns:
       raise ValueError(f'score: the target column {self.target_col!r} is not among the columns of the table')
     y = np.asarray(table[self.target_col].values, dtype=np.float64)
@@ -398,11 +407,15 @@ class BayesianNeuralFieldEstimator:
     rows = self.data_handler.get_test(table)
     out = inference.score_predictive(
         rows, y, self.observation_model, self.params_, self._model_args(rows.shape),
-        ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype)
+        ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype, rps=bool(rps))
     out['n'] = int(seen.size)
     for key in ('log_density', 'crps'):
       if key in out:
         out['mean_' + key] = float(np.mean(out[key][np.isfinite(y)], dtype=np.float64)) if seen.size else float('nan')
+    if rps:
+      kept = np.isfinite(y) & ~np.isnan(out['rps'])
+      out['rps_capped'] = int(seen.size - kept.sum())
+      out['mean_rps'] = float(np.mean(out['rps'][kept], dtype=np.float64)) if kept.any() else float('nan')
     return out
 
   def likelihood_model(self, table):

@@ -334,6 +334,23 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
                           const float* y, void* work, size_t work_bytes,
                           double* member_ll, float* lpd, float* pit, float* crps);
 
+/* The RANKED PROBABILITY SCORE of held-out counts y against the ensemble (handle created with BNF_OBS_NB / BNF_OBS_ZINB;
+ * BNF_ERR_INVALID on a NORMAL handle, whose CRPS bnf_predictive_scores has): the CRPS of a count forecast,
+ *   rps_r = sum_{k >= 0} (F_r(k) - 1{k >= y_r})^2,  F_r(k) = (1 / M) sum_m F_{m,r}(k)
+ * with the per-member laws of bnf_predictive_samples.  loc, aux, y as for bnf_predictive_scores; rps DEVICE (n_rows,) f32.
+ * The sum is taken term by term on a per-row window [a_r, b_r) and in closed form outside it, where every member's lower
+ * (below a_r) or upper (from b_r) tail is under 1e-9 (bnf_rps.h: how the window is found, the truncation bound).
+ * A row whose window is longer than BNF_RPS_MAX_TERMS gives NaN -- the work per row is bounded; a mean of 1e6 at
+ * total_count 0.05 would need 3e8 terms, and a strided or quadrature form for such rows is out of scope.  A row whose y is
+ * NaN, infinite, negative or not an integer gives NaN.  n_members <= BNF_RPS_MAX_MEMBERS (the members' running pmf and cdf
+ * live in LDS); BNF_ERR_INVALID above that, and for n_members < 1 or n_rows < 1.
+ * Everything after the f32 softplus is f64; every sum is in an order the shapes fix: no floating-point atomics, two calls
+ * give the same bits.  Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+#define BNF_RPS_MAX_TERMS (1 << 20)
+#define BNF_RPS_MAX_MEMBERS 2048
+int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                  const float* y, float* rps);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
