@@ -35,6 +35,7 @@
 #include "bnf_sampling.h"
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
+#include "bnf_totals.h"
 
 using namespace bnf;
 
@@ -1423,6 +1424,19 @@ static void launch_count_rps(bnf_handle* h, const float* loc, const float* aux, 
                      h->stream, loc, aux, (int32_t)M, R, y, rps);
 }
 
+// summaries of sample paths (bnf_totals.h): one workgroup per slab of C adjacent columns, C * P <= 16,384 doubles of LDS
+static void launch_sample_summaries(bnf_handle* h, const double* x, int64_t S, int64_t G, const double* y,
+                                    const SummaryQ& q, double* mean, double* quant, double* crps, double* pit) {
+  int P = 1;
+  while (P < S) P <<= 1;
+  const int C = std::min(kSumMaxCols, kSumMaxSamples / P);
+  const int threads = std::min(1024, std::max(64, C * P / 2));          // a multiple of 64: C * P is a power of two
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_sample_summaries, (int)(sizeof(double) * kSumMaxSamples), &attr_done);
+  hipLaunchKernelGGL(k_sample_summaries, dim3(cdiv(G, C)), dim3(threads), sizeof(double) * (size_t)C * (size_t)P, h->stream,
+                     x, (int32_t)S, G, (int32_t)P, (int32_t)C, y, q, mean, quant, crps, pit);
+}
+
 extern "C" {
 
 int bnf_abi_version(void) { return BNF_ABI_VERSION; }
@@ -2079,6 +2093,63 @@ int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_m
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.obs_model == BNF_OBS_NB) launch_count_rps<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, rps);
   else launch_count_rps<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, rps);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- summaries and scores of sample paths (bnf_totals.h) -----------------------------
+static int totals_args(const bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(BNF_ERR_NO_DEVICE, "no HIP device visible: the BayesNF engine has no CPU fallback (needs gfx950)");
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!x || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  if (n_samples > BNF_SUMMARY_MAX_SAMPLES)
+    return fail(BNF_ERR_INVALID, "%lld sample paths: a column is sorted in LDS, at most %d", (long long)n_samples,
+                BNF_SUMMARY_MAX_SAMPLES);
+  return BNF_OK;
+}
+
+int bnf_sample_summaries(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
+                         const double* q, int32_t n_q, double* mean, double* quant, double* crps, double* pit) {
+  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
+  if (n_q < 0 || n_q > BNF_SUMMARY_MAX_QUANTILES || (n_q > 0 && (!q || !quant)))
+    return fail(BNF_ERR_INVALID, "n_q = %d: 0..%d quantile levels, with q and quant", n_q, BNF_SUMMARY_MAX_QUANTILES);
+  if (!y && (crps || pit)) return fail(BNF_ERR_INVALID, "crps and pit need the observations y");
+  SummaryQ sq;
+  sq.n = n_q;
+  for (int32_t j = 0; j < kSumMaxQ; ++j) { sq.lo[j] = 0; sq.frac[j] = 0.0; }
+  for (int32_t j = 0; j < n_q; ++j) {
+    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(BNF_ERR_INVALID, "quantile level %g outside [0, 1]", q[j]);
+    const double hq = (double)(n_samples - 1) * q[j];
+    double lo = std::floor(hq);
+    double frac = hq - lo;
+    if (lo >= (double)(n_samples - 1)) { lo = (double)(n_samples - 1); frac = 0.0; }
+    sq.lo[j] = (int32_t)lo;
+    sq.frac[j] = frac;
+  }
+  if (!mean && !crps && !pit && n_q == 0) return BNF_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_sample_summaries(h, x, n_samples, n_cols, y, sq, mean, quant, crps, pit);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_sample_energy_score(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
+                            void* work, size_t work_bytes, double* out) {
+  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
+  if (!y || !out) return fail(BNF_ERR_INVALID, "argument");
+  const size_t need = sizeof(double) * (size_t)energy_work_doubles(n_samples);
+  if (!work || work_bytes < need)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld sample paths need %zu", work ? work_bytes : (size_t)0,
+                (long long)n_samples, need);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int64_t nT = energy_tiles(n_samples);
+  hipLaunchKernelGGL(k_energy_first, dim3((unsigned)n_samples), dim3(256), 0, h->stream, x, n_cols, y, (double*)work);
+  hipLaunchKernelGGL(k_energy_pairs, dim3((unsigned)nT, (unsigned)nT), dim3(256), 0, h->stream, x, n_samples, n_cols, y,
+                     (double*)work);
+  hipLaunchKernelGGL(k_energy_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, n_samples,
+                     nT * (nT + 1) / 2, y, n_cols, out);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -365,6 +365,61 @@ class Engine:
     torch.cuda.synchronize(self.device)     # the device copy of `y` is released on return
     return out
 
+  def _as_f64(self, a, shape, what):
+    t = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+         ).to(self.device, dtype=torch.float64).contiguous()
+    if shape is not None and tuple(t.shape) != shape:
+      raise ValueError(f'{what} must have shape {shape}; got {tuple(t.shape)}')
+    return t
+
+  def sample_summaries(self, x, y=None, q=()) -> dict:
+    """Column summaries of an ensemble of sample paths (include/bnf.h bnf_sample_summaries): x (S, G) f64 as
+    `predictive_group_sums` returns it, optionally the observed totals y (G,) -> dict of f64 device tensors:
+      'mean' (G,)            'quantiles' (len(q), G)   numpy's default 'linear' rule at the levels q
+      'crps' (G,)  'pit' (2, G)   with y only: the ensemble CRPS (V-statistic) and #{x <= y} / S, #{x < y} / S; NaN where
+                                  y is NaN
+    A column holding a NaN sample is NaN everywhere.  More than BNF_SUMMARY_MAX_SAMPLES paths, or a level outside [0, 1],
+    is the library's error (ValueError).  Deterministic: the same call gives the same bits."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, G = x.shape
+    y = None if y is None else self._as_f64(y, (G,), 'y')
+    levels = [float(v) for v in q]
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+    out = {'mean': f64(G), 'quantiles': f64(len(levels), G)}
+    if y is not None:
+      out['crps'], out['pit'] = f64(G), f64(2, G)
+    step = _native.SUMMARY_MAX_QUANTILES          # the levels of one call; more: further calls (each sorts again)
+    for j0 in range(0, max(1, len(levels)), step):
+      part = levels[j0:j0 + step]
+      first = j0 == 0
+      qa = (C.c_double * max(1, len(part)))(*part)
+      _native.check(self.lib.bnf_sample_summaries(
+          self.handle, _ptr(x), S, G, _ptr(y), qa, len(part), _ptr(out['mean'] if first else None),
+          _ptr(out['quantiles'][j0:j0 + step] if part else None), _ptr(out.get('crps') if first else None),
+          _ptr(out.get('pit') if first else None)), 'bnf_sample_summaries')
+    torch.cuda.synchronize(self.device)     # device copies of `x` and `y` made here are released on return
+    return out
+
+  def sample_energy_score(self, x, y) -> float:
+    """The energy score (1 / S) sum_s |X_s - y| - (1 / (2 S^2)) sum_st |X_s - X_t| of the joint paths x (S, G) f64
+    against the observed vector y (G,) (include/bnf.h bnf_sample_energy_score).  Columns whose y is NaN are left out of
+    both terms; NaN when none is left.  S^2 G / 2 differences.  Deterministic."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, G = x.shape
+    y = self._as_f64(y, (G,), 'y')
+    tiles = -(-S // _native.ENERGY_SAMPLE_TILE)
+    n_work = S + tiles * (tiles + 1) // 2                  # the formula of include/bnf.h
+    work = torch.empty(max(1, n_work), dtype=torch.float64, device=self.device)
+    out = torch.empty((1,), dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_sample_energy_score(
+        self.handle, _ptr(x), S, G, _ptr(y), _ptr(work), C.c_size_t(n_work * 8), _ptr(out)), 'bnf_sample_energy_score')
+    torch.cuda.synchronize(self.device)     # `work` is released on return
+    return float(out.cpu()[0])
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

@@ -363,6 +363,59 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
     eng.close()
 
 
+_TOTALS_MAX_CELLS = 1 << 28      # cells (sample x group, f64) of the totals matrix total_summaries holds on the device
+
+
+def total_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                    observed=None, quantiles=(), energy=True, compute_dtype=None):
+  """Group totals of the joint sample paths summarised and scored on the GPU: the (num_samples, G) matrix
+  `sample_predictive(..., groups=groups)` would return stays on the device (include/bnf.h bnf_predictive_group_sums) and
+  only the summaries come back (bnf_sample_summaries, bnf_sample_energy_score).  groups = (seg_offsets, seg_rows) as
+  `csr_from_codes` builds them; observed (G,) the observed totals, NaN where a group is not to be scored.
+  -> dict of float64 numpy arrays:
+    'mean' (G,)   'quantiles' (len(quantiles), G)   numpy's default 'linear' rule
+    'crps' (G,)   'pit' (2, G)                      with `observed`: the ensemble CRPS of every total and #{x <= y} / S,
+                                                    #{x < y} / S; NaN where observed is NaN
+    'energy_score' float                            with `observed` and energy=True: the energy score of the joint paths
+                                                    over the groups with an observed total (num_samples^2 G / 2 differences)
+  The matrix is held whole (the energy score needs every column): num_samples <= 16,384 (BNF_SUMMARY_MAX_SAMPLES: a
+  column is sorted in LDS) and num_samples * G <= 2^28 cells, ValueError beyond."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  if num_samples > _native.SUMMARY_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the totals are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
+                     'sample paths')
+  levels = [float(v) for v in quantiles]
+  if any(not 0.0 <= v <= 1.0 for v in levels):
+    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+  if observed is not None:
+    observed = np.ascontiguousarray(observed, dtype=np.float64)
+    if observed.shape != (n_groups,):
+      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  seed64 = _native.seed_to_u64(seed)
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
+                                       num_samples, seed64)
+    y = None if observed is None else torch.from_numpy(observed).to(eng.device)
+    res = eng.sample_summaries(totals, y, levels)
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    if y is not None and energy:
+      out['energy_score'] = eng.sample_energy_score(totals, y)
+    return out
+  finally:
+    eng.close()
+
+
 # ---------------------------------------------------------------------------
 # scores of held-out observations
 # ---------------------------------------------------------------------------

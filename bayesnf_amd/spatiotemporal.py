@@ -198,6 +198,20 @@ def group_rows(table, group_by):
   return keys, seg_offsets, seg_rows
 
 
+def group_target_sums(target, seg_offsets, seg_rows):
+  """Observed totals: the float64 sum of `target` (R,) over the rows of every group of the CSR layout `group_rows`
+  returns -> (G,); NaN for a group with a NaN target among its rows (and for an empty one, which `group_rows` never makes)."""
+  target = np.asarray(target, dtype=np.float64)
+  sorted_target = target[np.asarray(seg_rows, dtype=np.int64)]
+  starts = np.asarray(seg_offsets[:-1], dtype=np.int64)
+  sizes = np.diff(np.asarray(seg_offsets, dtype=np.int64))
+  out = np.full(len(starts), np.nan)
+  if sorted_target.size:
+    full = sizes > 0
+    out[full] = np.add.reduceat(sorted_target, starts[full])
+  return out
+
+
 # ---------------------------------------------------------------------------
 # estimators
 # ---------------------------------------------------------------------------
@@ -416,6 +430,61 @@ class BayesianNeuralFieldEstimator:
       kept = np.isfinite(y) & ~np.isnan(out['rps'])
       out['rps_capped'] = int(seen.size - kept.sum())
       out['mean_rps'] = float(np.mean(out['rps'][kept], dtype=np.float64)) if kept.any() else float('nan')
+    return out
+
+  def _total_summaries(self, what, table, group_by, quantiles, num_samples, seed, target=None, energy=False):
+    if int(num_samples) < 1:
+      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
+    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{what}: num_samples={num_samples}: the totals are summarised from at most '
+                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    keys, seg_offsets, seg_rows = group_rows(table, group_by)
+    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
+    rows = self.data_handler.get_test(table)
+    out = inference.total_summaries(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, quantiles=tuple(quantiles),
+        energy=bool(energy), compute_dtype=self.compute_dtype)
+    return out, keys, observed
+
+  def predict_totals(self, table, group_by, quantiles=(0.5,), num_samples=1000, seed=0):
+    """Mean and quantile bands of the group totals of `predict_samples(table, num_samples, seed, group_by=group_by)`,
+    summarised on the GPU: the (num_samples, G) matrix of totals never leaves the device.  -> (mean (G,), [one (G,) array
+    per level, numpy's default 'linear' quantile of the sampled totals], keys) with keys as in `predict_samples`.
+    num_samples <= 16,384."""
+    if self.params_ is None:
+      raise ValueError('predict_totals before fit')
+    out, keys, _ = self._total_summaries('predict_totals', table, group_by, quantiles, num_samples, seed)
+    return out['mean'], [out['quantiles'][i] for i in range(out['quantiles'].shape[0])], keys
+
+  def score_totals(self, table, group_by, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0, energy=True):
+    """The forecast of the group totals -- the sample paths of `predict_samples(table, num_samples, seed,
+    group_by=group_by)` -- scored against the observed totals of `table[target_col]`, on the GPU.  -> dict:
+      'keys'          the groups, as in `predict_samples`
+      'observed'      (G,) sum of the target over the group's rows; NaN when any row of the group has a NaN target: such
+                      a group is not scored
+      'mean'          (G,) mean of the sampled totals       'quantiles'  (len(quantiles), G) their 'linear' quantiles
+      'crps'          (G,) ensemble CRPS of every total, E|X - y| - E|X - X'| / 2 over the sample paths; NaN where not scored
+      'pit'           (2, G) share of the sampled totals <= and < the observed one (totals of counts tie)
+      'n'             number of groups scored       'mean_crps'  mean of 'crps' over them
+      'energy_score'  energy=True: the energy score of the joint paths over the scored groups, one number for the
+                      whole vector of totals (num_samples^2 G / 2 differences)
+    num_samples <= 16,384."""
+    if self.params_ is None:
+      raise ValueError('score_totals before fit')
+    if self.target_col not in table.columns:
+      raise ValueError(f'score_totals: the target column {self.target_col!r} is not among the columns of the table')
+    y = np.asarray(table[self.target_col].values, dtype=np.float64)
+    if np.isinf(y).any():
+      raise ValueError('score_totals: infinite targets')
+    seen = y[np.isfinite(y)]
+    if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
+      raise ValueError(f'score_totals: the {self.observation_model} observation model takes non-negative integer targets')
+    out, keys, observed = self._total_summaries(
+        'score_totals', table, group_by, quantiles, num_samples, seed, target=y, energy=energy)
+    scored = ~np.isnan(observed)
+    out.update(keys=keys, observed=observed, n=int(scored.sum()))
+    out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')
     return out
 
   def likelihood_model(self, table):

@@ -351,6 +351,43 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
 int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
                   const float* y, float* rps);
 
+/* SUMMARIES of an ensemble of sample paths, column by column: x DEVICE (n_samples, n_cols) f64 row-major -- the layout
+ * bnf_predictive_group_sums writes, one column per group total -- and optionally the observed totals y DEVICE (n_cols,)
+ * f64.  What a user of the totals would otherwise compute on the host from the whole matrix (np.quantile, an O(S^2) loop
+ * per group for the CRPS).  Every column is sorted in LDS (bnf_totals.h); outputs, each skipped when its pointer is NULL:
+ *   mean DEVICE (n_cols,) f64
+ *   quant DEVICE (n_q, n_cols) f64: the levels q, a HOST array of n_q doubles in [0, 1], by numpy's default ('linear') rule:
+ *     h = (n_samples - 1) q_j in f64, x_(floor h) + (h - floor h) (x_(floor h + 1) - x_(floor h)), exactly x_(h) when h is an
+ *     integer.  n_q <= BNF_SUMMARY_MAX_QUANTILES per call (the levels travel as a kernel argument); required for n_q > 0
+ *   pit DEVICE (2, n_cols) f64: [0] = #{x_s <= y_c} / n_samples, [1] = #{x_s < y_c} / n_samples
+ *   crps DEVICE (n_cols,) f64: the ensemble CRPS E|X - y| - E|X - X'| / 2 as a V-statistic,
+ *     (1 / S) sum_s |x_s - y_c| - (1 / S^2) sum_{i = 1..S} (2 i - S - 1) x_(i), evaluated on x - y_c
+ * A column whose y_c is NaN or infinite gives NaN in crps and pit (mean and quant are still produced); a column that holds
+ * a NaN sample gives NaN in every output.  y == NULL: a pure summary, crps and pit must be NULL too (BNF_ERR_INVALID).
+ * n_samples <= BNF_SUMMARY_MAX_SAMPLES (a sorted column is 128 KiB of the CU's 160 KiB of LDS; a multi-pass sort is out
+ * of scope); BNF_ERR_INVALID above that, for n_samples < 1, n_cols < 1, n_q < 0 and for a level outside [0, 1].
+ * Everything is f64, every sum in an order the shapes fix: no atomics, two calls give the same bits.  No work buffer.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles; the observation model of
+ * the handle plays no part. */
+#define BNF_SUMMARY_MAX_SAMPLES 16384
+#define BNF_SUMMARY_MAX_QUANTILES 64
+int bnf_sample_summaries(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
+                         const double* q, int32_t n_q, double* mean, double* quant, double* crps, double* pit);
+
+/* The ENERGY SCORE of the joint sample paths against the observed vector, one number per call:
+ *   out[0] = (1 / S) sum_s |X_s - y|_2 - (1 / (2 S^2)) sum_{s,t} |X_s - X_t|_2,   X_s = row s of x, S = n_samples
+ * x, y as for bnf_sample_summaries (y required); out DEVICE (1,) f64.  The norms run over the columns whose y_c is finite,
+ * the others are skipped in both terms; no finite y_c at all gives NaN.  Every distance is formed from direct differences
+ * in f64; the cost is n_samples^2 n_cols / 2 differences (the pairs s < t, doubled).
+ *   work DEVICE, work_bytes: one |X_s - y| per path and one partial sum per 64 x 64 tile of pairs on or above the diagonal,
+ *     8 * (n_samples + T (T + 1) / 2) bytes, T = ceil(n_samples / BNF_ENERGY_SAMPLE_TILE); BNF_ERR_INVALID below that
+ * n_samples <= BNF_SUMMARY_MAX_SAMPLES; BNF_ERR_INVALID above that and for n_samples < 1 or n_cols < 1.  The partial sums
+ * are added in index order: no atomics, two calls give the same bits.  Runs on the handle's stream, does not touch the
+ * training state, works on forward-only handles. */
+#define BNF_ENERGY_SAMPLE_TILE 64
+int bnf_sample_energy_score(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
+                            void* work, size_t work_bytes, double* out);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
