@@ -25,6 +25,14 @@ RPS_MAX_TERMS, RPS_MAX_MEMBERS = 1 << 20, 2048   # BNF_RPS_*: longest window / m
 # side of a pair tile of bnf_sample_energy_score (sizes its work buffer)
 SUMMARY_MAX_SAMPLES, SUMMARY_MAX_QUANTILES, ENERGY_SAMPLE_TILE = 16384, 64, 64
 GROUP_TILE = 1024   # BNF_GROUP_TILE: rows per partial sum of bnf_predictive_group_sums (sizes its work buffer)
+STACK_ROW_TILE, STACK_STATE_DOUBLES = 1024, 8   # BNF_STACK_*: size the work buffer of bnf_stacking_weights
+
+
+def stacking_work_doubles(n_members: int, n_rows: int) -> int:
+  """Doubles of the work buffer of bnf_stacking_weights (the formula of include/bnf.h)."""
+  return STACK_STATE_DOUBLES + (int(n_members) + 3) * (-(-int(n_rows) // STACK_ROW_TILE))
+
+
 # 'fp32' (= 'f32', 'float32', 'fp32_exact') = BNF_DTYPE_F32: the exact f32 MFMA chain -- what an explicit 'fp32' always means
 # (round 5 had silently mapped it to the split form: ADVICE r05); 'fp32_split' (= 'bf16x3') = BNF_DTYPE_F32S: f32 storage /
 # accumulation / epilogues with the contractions on split-bf16 MFMAs (16 operand bits, ~5e-6 per contraction against 1e-7;
@@ -42,6 +50,8 @@ EXPORTS = (
     'bnf_init_params', 'bnf_init_params_keys', 'bnf_train', 'bnf_row_tables', 'bnf_row_keys', 'bnf_vi_posterior_draws', 'bnf_vi_noise_keys', 'bnf_forward',
     'bnf_normal_mixture_quantiles', 'bnf_count_mixture_quantiles', 'bnf_predictive_samples', 'bnf_predictive_group_sums',
     'bnf_predictive_scores', 'bnf_count_rps', 'bnf_sample_summaries', 'bnf_sample_energy_score',
+    'bnf_member_log_density', 'bnf_stacking_weights', 'bnf_predictive_samples_weighted',
+    'bnf_predictive_group_sums_weighted',
     'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
@@ -138,6 +148,11 @@ def load():
   lib.bnf_count_rps.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_sample_summaries.argtypes = [vp, vp, i64, i64, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
   lib.bnf_sample_energy_score.argtypes = [vp, vp, i64, i64, vp, vp, C.c_size_t, vp]
+  lib.bnf_member_log_density.argtypes = [vp, vp, vp, i64, i64, vp, vp]
+  lib.bnf_stacking_weights.argtypes = [vp, vp, i64, i64, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
+  lib.bnf_predictive_samples_weighted.argtypes = [vp, vp, vp, i64, i64, i64, C.c_uint64, i64, i64, vp, vp]
+  lib.bnf_predictive_group_sums_weighted.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp,
+                                                     C.c_size_t, vp]
   lib.bnf_debug_loss_and_grad.argtypes = [vp, i64, i64, vp, vp]
   lib.bnf_debug_row_index.argtypes = [vp, i64, i64, vp]
   lib.bnf_debug_vi_eps.argtypes = [vp, i64, vp]

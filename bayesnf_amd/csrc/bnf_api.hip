@@ -36,6 +36,7 @@
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
+#include "bnf_stacking.h"
 
 using namespace bnf;
 
@@ -1372,21 +1373,22 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
 // posterior-predictive sampling launches (bnf_sampling.h), one instantiation per observation model
 template <int OBS>
 static void launch_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, int64_t S,
-                                      uint64_t seed, int64_t row0, int64_t sample0, float* out) {
+                                      uint64_t seed, int64_t row0, int64_t sample0, const double* cum, float* out) {
   const int64_t gx = cdiv(R, 256 * kPredRowsPerThread);
   const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));
   hipLaunchKernelGGL((k_predictive_samples<OBS>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
-                     (int32_t)M, R, S, seed, row0, sample0, out);
+                     (int32_t)M, R, S, seed, row0, sample0, cum, out);
 }
 
 template <int OBS>
 static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
                                          const int32_t* seg_offsets, const int32_t* seg_rows, int64_t G, int64_t S,
-                                         uint64_t seed, int64_t row0, int64_t sample0, double* partial, double* out) {
+                                         uint64_t seed, int64_t row0, int64_t sample0, const double* cum, double* partial,
+                                         double* out) {
   const int64_t nt = cdiv(R, kPredTile);
   const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
   hipLaunchKernelGGL((k_predictive_group_sums<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
-                     (int32_t)M, R, seg_offsets, seg_rows, (int32_t)G, S, seed, row0, sample0, partial, out);
+                     (int32_t)M, R, seg_offsets, seg_rows, (int32_t)G, S, seed, row0, sample0, cum, partial, out);
   hipLaunchKernelGGL(k_predictive_group_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
                      seg_offsets, (int32_t)G, R, S, partial, out);
 }
@@ -2008,23 +2010,30 @@ static int predictive_args(const bnf_handle* h, const float* loc, const float* a
   return BNF_OK;
 }
 
-int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                           int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, float* out) {
+static int predictive_samples_impl(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                   int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, const double* cum,
+                                   float* out) {
   if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
   if (!out) return fail(BNF_ERR_INVALID, "argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   switch (h->cfg.obs_model) {
-    case BNF_OBS_NORMAL: launch_predictive_samples<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
-    case BNF_OBS_NB: launch_predictive_samples<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
-    default: launch_predictive_samples<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, out); break;
+    case BNF_OBS_NORMAL: launch_predictive_samples<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
+    case BNF_OBS_NB: launch_predictive_samples<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
+    default: launch_predictive_samples<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
   }
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
 
-int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                              const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                              uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out) {
+int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, float* out) {
+  return predictive_samples_impl(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, nullptr, out);
+}
+
+static int predictive_group_sums_impl(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                      const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
+                                      int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, const double* cum,
+                                      void* work, size_t work_bytes, double* out) {
   if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
   if (!seg_offsets || !seg_rows || !work || !out || n_groups < 1 || n_groups > 0x7fffffffLL)
     return fail(BNF_ERR_INVALID, "argument");
@@ -2040,13 +2049,44 @@ int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux,
     const int64_t n = std::min(chunk, n_samples - s0);
     double* o = out + s0 * n_groups;
     switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_group_sums<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
-      case BNF_OBS_NB: launch_predictive_group_sums<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
-      default: launch_predictive_group_sums<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, (double*)work, o); break;
+      case BNF_OBS_NORMAL: launch_predictive_group_sums<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
+      case BNF_OBS_NB: launch_predictive_group_sums<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
+      default: launch_predictive_group_sums<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
     }
   }
   HIPCHK(hipGetLastError());
   return BNF_OK;
+}
+
+int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                              const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                              uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out) {
+  return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
+                                    sample0, nullptr, work, work_bytes, out);
+}
+
+// the same paths with member weights: cum_weights DEVICE (n_members,) f64 running sum, NULL = the calls above
+static int no_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(BNF_ERR_NO_DEVICE, "no HIP device visible: the BayesNF engine has no CPU fallback (needs gfx950)");
+  return BNF_OK;
+}
+
+int bnf_predictive_samples_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                    const double* cum_weights, float* out) {
+  if (const int rc = no_device()) return rc;
+  return predictive_samples_impl(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum_weights, out);
+}
+
+int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                       const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
+                                       int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                       const double* cum_weights, void* work, size_t work_bytes, double* out) {
+  if (const int rc = no_device()) return rc;
+  return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
+                                    sample0, cum_weights, work, work_bytes, out);
 }
 
 // ---- held-out scoring (bnf_scoring.h) ---------------------------------------------
@@ -2075,6 +2115,69 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
     case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
     default: launch_predictive_scores<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
   }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- stacking of the members on held-out rows (bnf_stacking.h) ----------------------
+int bnf_member_log_density(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           const float* y, float* out) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!loc || !aux || !y || !out || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const dim3 grid(cdiv(n_rows, kStackTile), (unsigned)std::min<int64_t>(n_members, 65535));
+  switch (h->cfg.obs_model) {
+    case BNF_OBS_NORMAL: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_NORMAL>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
+    case BNF_OBS_NB: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_NB>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
+    default: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_ZINB>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members, int64_t n_rows, const double* w_init,
+                         int64_t max_iter, double tol, void* work, size_t work_bytes, double* weights, float* lpd,
+                         double* info) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!logdens || !weights || !info || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (max_iter < 0 || !(tol >= 0.0)) return fail(BNF_ERR_INVALID, "max_iter = %lld, tol = %g: both must be >= 0",
+                                                  (long long)max_iter, tol);
+  const int64_t nt = cdiv(n_rows, kStackTile);
+  const size_t need = sizeof(double) * ((size_t)kStackState + (size_t)(n_members + 3) * (size_t)nt);
+  if (!work || work_bytes < need)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld members x %lld rows need %zu", work ? work_bytes : (size_t)0,
+                (long long)n_members, (long long)n_rows, need);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  double* state = (double*)work;
+  double* tile_stat = state + kStackState;
+  double* partial = tile_stat + 3 * nt;
+  const int32_t M = (int32_t)n_members;
+  hipLaunchKernelGGL(k_stack_init, dim3(1), dim3(256), 0, h->stream, w_init, M, weights, state);
+  // max_iter updates need max_iter + 1 evaluations: the last one is of the weights that are returned
+  bool done = false;
+  for (int64_t left = max_iter + 1; left > 0 && !done;) {
+    const int64_t batch = std::min<int64_t>(left, BNF_STACK_BATCH);
+    for (int64_t i = 0; i < batch; ++i) {
+      hipLaunchKernelGGL((k_stack_rows<false>), dim3((unsigned)nt), dim3(256), 0, h->stream, logdens, M, n_rows,
+                         (const double*)weights, (const double*)state, partial, tile_stat, (float*)nullptr);
+      hipLaunchKernelGGL(k_stack_combine, dim3(1), dim3(256), 0, h->stream, (const double*)partial,
+                         (const double*)tile_stat, M, nt, max_iter, tol, weights, state, info);
+    }
+    left -= batch;
+    HIPCHK(hipGetLastError());
+    double flag = 0.0;
+    HIPCHK(hipMemcpyAsync(&flag, state + STACK_DONE, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    done = flag != 0.0;
+  }
+  if (!done) return fail(BNF_ERR_STATE, "stacking: the iteration budget ran out without the stop being recorded");
+  if (lpd)
+    hipLaunchKernelGGL((k_stack_rows<true>), dim3((unsigned)nt), dim3(256), 0, h->stream, logdens, M, n_rows,
+                       (const double*)weights, (const double*)state, (double*)nullptr, (double*)nullptr, lpd);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -2,7 +2,8 @@
 // bnf_predictive_group_sums): joint draws of the equal-weight mixture over members that `predict` reports
 // marginal quantiles of.  What the reference gets from TFP's `.sample()` on its `likelihood_model()`.
 //
-//   sample path s  : ONE mixture component c_s = floor(u M) for every row, u a Philox draw keyed by (seed, s)
+//   sample path s  : ONE mixture component c_s = floor(u M) for every row, u a Philox draw keyed by (seed, s); with
+//                    member weights (the *_weighted entry points) c_s = #{m : cum[m] <= u}, cum their running sum
 //   row r of path s: an independent draw from member c_s's distribution at that row
 //       NORMAL  N(loc, aux[0])
 //       NB      total_count = 1 / aux[1], logits = -log aux[1] - log softplus(loc), drawn as
@@ -45,10 +46,26 @@ __device__ __forceinline__ Philox pred_bits(uint64_t seed, uint32_t s, uint64_t 
                     (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
-// mixture component of sample path s: floor(u M), u = word / 2^32
+// mixture component of sample path s, equal weights: floor(u M), u = word / 2^32
 __device__ __forceinline__ int32_t pred_component(uint64_t seed, uint32_t s, int32_t M) {
   const Philox b = philox4x32(s, 0u, 0u, (uint32_t)STREAM_PRED_COMPONENT, (uint32_t)seed, (uint32_t)(seed >> 32));
   return (int32_t)(((uint64_t)b.v[0] * (uint64_t)(uint32_t)M) >> 32);
+}
+
+// weighted form: cum (M,) f64 the running sum of the member weights (nondecreasing, last entry 1), the same Philox word,
+// u = word / 2^32 and c_s = #{m : cum[m] <= u} by bisection, clamped to M - 1: whatever cum holds, the result is a
+// member, never an index outside loc.  u moves in steps of 2^-32: a member whose weight is below 2^-32 may own no u at
+// all and is then never drawn.  cum == nullptr: the integer form above (the equal-weight entry points keep their bits).
+__device__ __forceinline__ int32_t pred_component(uint64_t seed, uint32_t s, int32_t M, const double* __restrict__ cum) {
+  if (!cum) return pred_component(seed, s, M);
+  const Philox b = philox4x32(s, 0u, 0u, (uint32_t)STREAM_PRED_COMPONENT, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const double u = (double)b.v[0] * 2.3283064365386963e-10;   // 2^-32, exact
+  int32_t lo = 0, hi = M;                                      // cum[m] <= u for m < lo, cum[m] > u for m >= hi
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (cum[mid] <= u) lo = mid + 1; else hi = mid;
+  }
+  return lo < M - 1 ? lo : M - 1;
 }
 
 // log of a Gamma(shape a, scale 1) draw: Marsaglia & Tsang (2000) on shape a (+ 1 where a < 1, then times U^(1/a)).
@@ -149,11 +166,12 @@ __device__ __forceinline__ float predictive_draw(uint64_t seed, uint32_t s, uint
 template <int OBS>
 __global__ __launch_bounds__(256) void k_predictive_samples(const float* __restrict__ loc, const float* __restrict__ aux,
                                                             int32_t M, int64_t R, int64_t S, uint64_t seed, int64_t row0,
-                                                            int64_t sample0, float* __restrict__ out) {
+                                                            int64_t sample0, const double* __restrict__ cum,
+                                                            float* __restrict__ out) {
   const int64_t base = (int64_t)blockIdx.x * (256 * kPredRowsPerThread) + threadIdx.x;
   for (int64_t s = blockIdx.y; s < S; s += gridDim.y) {
     const uint32_t sg = (uint32_t)(sample0 + s);
-    const int32_t c = pred_component(seed, sg, M);
+    const int32_t c = pred_component(seed, sg, M, cum);
     const float a0 = aux[c * 3], a1 = aux[c * 3 + 1], a2 = aux[c * 3 + 2];
     const float* lrow = loc + (int64_t)c * R;
     float* orow = out + s * R;
@@ -209,7 +227,8 @@ template <int OBS>
 __global__ __launch_bounds__(256) void k_predictive_group_sums(
     const float* __restrict__ loc, const float* __restrict__ aux, int32_t M, int64_t R,
     const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ seg_rows, int32_t G, int64_t S, uint64_t seed,
-    int64_t row0, int64_t sample0, double* __restrict__ partial, double* __restrict__ out) {
+    int64_t row0, int64_t sample0, const double* __restrict__ cum, double* __restrict__ partial,
+    double* __restrict__ out) {
   __shared__ double xs[2][kPredTile];
   __shared__ double wsum[2][4];
   __shared__ int s_maxlen, s_kind, s_g;
@@ -253,7 +272,7 @@ __global__ __launch_bounds__(256) void k_predictive_group_sums(
   int it = 0;
   for (int64_t s = blockIdx.y; s < S; s += gridDim.y, ++it) {
     const uint32_t sg = (uint32_t)(sample0 + s);
-    const int32_t c = pred_component(seed, sg, M);
+    const int32_t c = pred_component(seed, sg, M, cum);
     const float a0 = aux[c * 3], a1 = aux[c * 3 + 1], a2 = aux[c * 3 + 2];
     const float* lrow = loc + (int64_t)c * R;
     double v[kPredRowsPerThread];

@@ -268,26 +268,42 @@ class Engine:
         _ptr(means), _ptr(out)), 'bnf_count_mixture_quantiles')
     return means, out
 
+  def _cum(self, cum_weights, M):
+    """cum_weights (M,) -> f64 device tensor (None stays None: the equal-weight call)."""
+    if cum_weights is None:
+      return None
+    return self._as_f64(cum_weights, (M,), 'cum_weights')
+
   def predictive_samples(self, loc: torch.Tensor, aux: torch.Tensor, n_samples: int, seed, row0=0,
-                         sample0=0) -> torch.Tensor:
+                         sample0=0, cum_weights=None) -> torch.Tensor:
     """Posterior-predictive sample paths (include/bnf.h bnf_predictive_samples): loc (M, R), aux (M, 3) as `forward`
     returns them -> (n_samples, R) f32 on the device.  Path s draws one member for all rows, then every row from that
     member's observation model.  row0 / sample0: global index of loc's first column / of the first path -- the values
-    are a pure function of (seed, path, global row), so chunks of any size reproduce the one big call."""
+    are a pure function of (seed, path, global row), so chunks of any size reproduce the one big call.
+    cum_weights (M,) f64: the running sum of member weights (nondecreasing, last entry 1; bnf_predictive_samples_weighted):
+    path s draws member #{m : cum[m] <= u} instead of floor(u M).  None: the equal-weight call, bit for bit."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
     out = torch.empty((int(n_samples), R), dtype=torch.float32, device=self.device)
-    _native.check(self.lib.bnf_predictive_samples(
+    if cum_weights is None:
+      _native.check(self.lib.bnf_predictive_samples(
+          self.handle, _ptr(loc), _ptr(aux), M, R, int(n_samples), C.c_uint64(_native.seed_to_u64(seed)), int(row0),
+          int(sample0), _ptr(out)), 'bnf_predictive_samples')
+      return out
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_samples_weighted(
         self.handle, _ptr(loc), _ptr(aux), M, R, int(n_samples), C.c_uint64(_native.seed_to_u64(seed)), int(row0),
-        int(sample0), _ptr(out)), 'bnf_predictive_samples')
+        int(sample0), _ptr(cum), _ptr(out)), 'bnf_predictive_samples_weighted')
+    torch.cuda.synchronize(self.device)     # the device copy of `cum_weights` is released on return
     return out
 
   def predictive_group_sums(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
-                            row0=0, sample0=0) -> torch.Tensor:
+                            row0=0, sample0=0, cum_weights=None) -> torch.Tensor:
     """Totals of the same sample paths over groups of rows (include/bnf.h bnf_predictive_group_sums) -> (n_samples, G)
     f64 on the device, without materialising the draws.  The rows come sorted by group as CSR: seg_offsets (G + 1),
-    seg_rows (R) int32 (`inference.csr_from_codes`).  Deterministic: the same call gives the same bits."""
+    seg_rows (R) int32 (`inference.csr_from_codes`).  Deterministic: the same call gives the same bits.
+    cum_weights as for `predictive_samples` (bnf_predictive_group_sums_weighted); None: the equal-weight call."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
@@ -303,10 +319,17 @@ class Engine:
     per_path = 2 * (-(-R // _native.GROUP_TILE))
     work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // (8 * per_path))), dtype=torch.float64,
                        device=self.device)
-    _native.check(self.lib.bnf_predictive_group_sums(
-        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
-        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(work), C.c_size_t(work.numel() * 8),
-        _ptr(out)), 'bnf_predictive_group_sums')
+    if cum_weights is None:
+      _native.check(self.lib.bnf_predictive_group_sums(
+          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(work), C.c_size_t(work.numel() * 8),
+          _ptr(out)), 'bnf_predictive_group_sums')
+    else:
+      cum = self._cum(cum_weights, M)
+      _native.check(self.lib.bnf_predictive_group_sums_weighted(
+          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(work),
+          C.c_size_t(work.numel() * 8), _ptr(out)), 'bnf_predictive_group_sums_weighted')
     torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
     return out
 
@@ -363,6 +386,53 @@ class Engine:
     out = torch.empty((R,), dtype=torch.float32, device=self.device)
     _native.check(self.lib.bnf_count_rps(self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(out)), 'bnf_count_rps')
     torch.cuda.synchronize(self.device)     # the device copy of `y` is released on return
+    return out
+
+  def member_log_density(self, loc: torch.Tensor, aux: torch.Tensor, y) -> torch.Tensor:
+    """log p_m(y_r) of every member at every row (include/bnf.h bnf_member_log_density): loc (M, R), aux (M, 3) as
+    `forward` returns them, y (R,) -> (M, R) f32 on the device -- the terms `predictive_scores` sums into 'member_ll'.
+    NaN in every member of a row whose y is not finite; -inf where a member gives the observation density 0."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    y = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
+         ).to(self.device, dtype=torch.float32).contiguous()
+    if y.shape != (R,):
+      raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
+    out = torch.empty((M, R), dtype=torch.float32, device=self.device)
+    _native.check(self.lib.bnf_member_log_density(self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(out)),
+                  'bnf_member_log_density')
+    torch.cuda.synchronize(self.device)     # the device copy of `y` is released on return
+    return out
+
+  def stacking_weights(self, logdens: torch.Tensor, w_init=None, max_iter=10000, tol=1e-5, lpd=True) -> dict:
+    """Stacking weights of the members (include/bnf.h bnf_stacking_weights): logdens (M, R) f32 as `member_log_density`
+    returns it -> the simplex weights that maximise the mean over the scored rows of log sum_m w_m p_m(y_r), by EM from
+    w_init (None: uniform), stopped at gap = max_m g_m - 1 <= tol (a bound on the distance of the objective from its
+    optimum) or after max_iter updates.  max_iter=0 evaluates w_init.  -> dict:
+      'weights' (M,) f64 device tensor   'lpd' (R,) f32 device tensor with lpd=True: the log density of the weighted
+                                         mixture; NaN rows NaN, dropped rows -inf
+      'objective', 'objective_start', 'gap' floats   'iterations', 'dropped' ints   'converged' gap <= tol
+    A row is dropped when every member with a positive weight gives it the density 0.  Deterministic."""
+    logdens = logdens.contiguous().float()
+    if logdens.dim() != 2:
+      raise ValueError(f'logdens must be (n_members, n_rows); got {tuple(logdens.shape)}')
+    M, R = logdens.shape
+    w0 = None if w_init is None else self._as_f64(w_init, (M,), 'w_init')
+    weights = torch.empty((M,), dtype=torch.float64, device=self.device)
+    info = torch.empty((5,), dtype=torch.float64, device=self.device)
+    out_lpd = torch.empty((R,), dtype=torch.float32, device=self.device) if lpd else None
+    n_work = _native.stacking_work_doubles(M, R)
+    work = torch.empty(n_work, dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_stacking_weights(
+        self.handle, _ptr(logdens), M, R, _ptr(w0), int(max_iter), C.c_double(float(tol)), _ptr(work),
+        C.c_size_t(n_work * 8), _ptr(weights), _ptr(out_lpd), _ptr(info)), 'bnf_stacking_weights')
+    torch.cuda.synchronize(self.device)     # `work` and the device copy of `w_init` are released on return
+    f, f0, gap, iters, dropped = info.cpu().tolist()
+    out = {'weights': weights, 'objective': f, 'objective_start': f0, 'gap': gap, 'iterations': int(iters),
+           'dropped': int(dropped), 'converged': bool(gap <= float(tol))}
+    if lpd:
+      out['lpd'] = out_lpd
     return out
 
   def _as_f64(self, a, shape, what):

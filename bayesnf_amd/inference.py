@@ -328,8 +328,37 @@ def csr_from_codes(codes, n_groups):
   return seg_offsets.astype(np.int32), seg_rows.astype(np.int32)
 
 
+def mixture_weights(weights, params, ensemble_dims):
+  """Member weights checked and flattened: `weights` must have the shape of the leading ensemble dims of `params` (what
+  `member_log_prob` of score_predictive has; for VI the posterior draws count as components), every entry finite and >= 0,
+  the sum within 1e-9 of 1; anything else is a ValueError.  -> (w (M,), cum (M,)) float64, flattened in the order the
+  members are flattened everywhere else; cum = cumsum(w) with the last entry set to exactly 1, the form the sampling
+  kernels take (include/bnf.h bnf_predictive_samples_weighted).  weights=None -> (None, None): equal weights.
+  A weight below 2^-32 is never drawn by the sampling kernels."""
+  if weights is None:
+    return None, None
+  lead = tuple(np.shape(params[0])[:ensemble_dims])
+  try:
+    w = np.asarray(weights, dtype=np.float64)
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'weights must be an array of numbers of shape {lead}') from e
+  if w.shape != lead:
+    raise ValueError(f'weights must have the shape of the ensemble dims of the fitted parameters {lead}; got {w.shape}')
+  if not np.all(np.isfinite(w)):
+    raise ValueError('weights must be finite')
+  if np.any(w < 0):
+    raise ValueError('weights must be >= 0')
+  total = float(np.sum(w, dtype=np.float64))
+  if abs(total - 1.0) > 1e-9:
+    raise ValueError(f'weights must sum to 1 (within 1e-9); got {total!r}')
+  w = np.ascontiguousarray(w.reshape(-1))
+  cum = np.cumsum(w, dtype=np.float64)
+  cum[-1] = 1.0
+  return w, cum
+
+
 def sample_predictive(features, observation_model, params, model_args, num_samples, seed, ensemble_dims,
-                      groups=None, compute_dtype=None):
+                      groups=None, compute_dtype=None, weights=None):
   """Joint posterior-predictive draws on the GPU (include/bnf.h bnf_predictive_samples / bnf_predictive_group_sums;
   the reference draws with `.sample()` on its `likelihood_model()`).  Every leading ensemble dim of `params` --
   devices, members, and for VI the posterior draws -- flattens to the M equally weighted mixture components, exactly
@@ -338,10 +367,14 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
     groups=(seg_offsets, seg_rows)   -> (num_samples, G) float64 totals per group (`csr_from_codes`), summed on the
                                         device without materialising the draws
   The rows are drawn in chunks of _SAMPLE_CHUNK_CELLS // num_samples so that the device buffer stays bounded; the
-  values do not depend on the chunking (counter-based generator keyed by seed, path and global row)."""
+  values do not depend on the chunking (counter-based generator keyed by seed, path and global row).
+  weights (shape of the ensemble dims, `mixture_weights`): path s draws its component with these probabilities instead
+  of equal ones -- the weights `stack_members` returns.  None: nothing changes."""
   num_samples = int(num_samples)
   if num_samples < 1:
     raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
   seed64 = _native.seed_to_u64(seed)
   features = np.asarray(features, dtype=np.float64)
   n_rows = features.shape[0]
@@ -352,12 +385,12 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
   try:
     if groups is not None:
       seg_offsets, seg_rows = groups
-      return eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64).cpu().numpy()
+      return eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw).cpu().numpy()
     out = np.empty((num_samples, n_rows), dtype=np.float32)
     chunk = max(1, _SAMPLE_CHUNK_CELLS // num_samples)
     for r0 in range(0, n_rows, chunk):
       r1 = min(n_rows, r0 + chunk)
-      out[:, r0:r1] = eng.predictive_samples(loc[:, r0:r1], aux, num_samples, seed64, row0=r0).cpu().numpy()
+      out[:, r0:r1] = eng.predictive_samples(loc[:, r0:r1], aux, num_samples, seed64, row0=r0, **kw).cpu().numpy()
     return out
   finally:
     eng.close()
@@ -367,7 +400,7 @@ _TOTALS_MAX_CELLS = 1 << 28      # cells (sample x group, f64) of the totals mat
 
 
 def total_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
-                    observed=None, quantiles=(), energy=True, compute_dtype=None):
+                    observed=None, quantiles=(), energy=True, compute_dtype=None, weights=None):
   """Group totals of the joint sample paths summarised and scored on the GPU: the (num_samples, G) matrix
   `sample_predictive(..., groups=groups)` would return stays on the device (include/bnf.h bnf_predictive_group_sums) and
   only the summaries come back (bnf_sample_summaries, bnf_sample_energy_score).  groups = (seg_offsets, seg_rows) as
@@ -379,7 +412,8 @@ def total_summaries(features, observation_model, params, model_args, num_samples
     'energy_score' float                            with `observed` and energy=True: the energy score of the joint paths
                                                     over the groups with an observed total (num_samples^2 G / 2 differences)
   The matrix is held whole (the energy score needs every column): num_samples <= 16,384 (BNF_SUMMARY_MAX_SAMPLES: a
-  column is sorted in LDS) and num_samples * G <= 2^28 cells, ValueError beyond."""
+  column is sorted in LDS) and num_samples * G <= 2^28 cells, ValueError beyond.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights, nothing changes."""
   num_samples = int(num_samples)
   if num_samples < 1:
     raise ValueError(f'num_samples={num_samples}: need at least one sample path')
@@ -398,6 +432,8 @@ def total_summaries(features, observation_model, params, model_args, num_samples
     observed = np.ascontiguousarray(observed, dtype=np.float64)
     if observed.shape != (n_groups,):
       raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
   seed64 = _native.seed_to_u64(seed)
   features = np.asarray(features, dtype=np.float64)
   n_rows = features.shape[0]
@@ -405,7 +441,7 @@ def total_summaries(features, observation_model, params, model_args, num_samples
       features, observation_model, params, model_args, ensemble_dims, compute_dtype)
   try:
     totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                       num_samples, seed64)
+                                       num_samples, seed64, **kw)
     y = None if observed is None else torch.from_numpy(observed).to(eng.device)
     res = eng.sample_summaries(totals, y, levels)
     out = {k: v.cpu().numpy() for k, v in res.items()}
@@ -451,6 +487,43 @@ def score_predictive(features, target, observation_model, params, model_args, en
       out['crps'] = res['crps'].cpu().numpy()
     if rps:
       out['rps'] = eng.count_rps(loc, aux, y32).cpu().numpy()
+    return out
+  finally:
+    eng.close()
+
+
+def stack_members(features, target, observation_model, params, model_args, ensemble_dims, weights=None, max_iter=10000,
+                  tol=1e-5, compute_dtype=None):
+  """Stacking of the members on held-out rows, on the GPU (include/bnf.h bnf_member_log_density, bnf_stacking_weights):
+  the simplex weights over the M flattened members (VI: posterior draws count as components) that maximise the mean log
+  density of `target` under the weighted mixture, found by EM from `weights` (None: equal weights) and stopped when
+  gap = max_m g_m - 1 <= tol -- a bound on how far the objective is from its optimum -- or after max_iter updates.
+  max_iter=0 evaluates `weights` as they are.  NaN targets are allowed: their rows are left out.  -> dict:
+    'weights'          leading ensemble dims of `params`, float64
+    'log_density'      (n_rows,) float32 log density of the weighted mixture; NaN rows NaN, dropped rows -inf
+    'objective', 'objective_start'   mean log density over the scored rows at the returned / the starting weights
+    'gap', 'iterations', 'converged', 'dropped'   dropped: rows to which every member with a positive weight gives the
+                                                  density 0 (left out of the means)
+  Only the sample-path family takes the weights (`sample_predictive`, `total_summaries`): the marginal quantiles of
+  predict_bnf and the pit / crps / rps of score_predictive stay those of the equal-weight mixture, and fit is untouched."""
+  w0, _ = mixture_weights(weights, params, ensemble_dims)
+  max_iter = int(max_iter)
+  tol = float(tol)
+  if max_iter < 0 or not tol >= 0.0:
+    raise ValueError(f'max_iter={max_iter}, tol={tol}: both must be >= 0')
+  features = np.asarray(features, dtype=np.float64)
+  target = np.asarray(target, dtype=np.float64)
+  n_rows = features.shape[0]
+  if target.shape != (n_rows,):
+    raise ValueError(f'target must hold one observation per row ({n_rows},); got {target.shape}')
+  net, eng, lead, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    loc, aux, y32 = loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), np.ascontiguousarray(target, dtype=np.float32)
+    res = eng.stacking_weights(eng.member_log_density(loc, aux, y32), w_init=w0, max_iter=max_iter, tol=tol)
+    out = {k: res[k] for k in ('objective', 'objective_start', 'gap', 'iterations', 'converged', 'dropped')}
+    out['weights'] = res['weights'].cpu().numpy().reshape(tuple(lead))
+    out['log_density'] = res['lpd'].cpu().numpy()
     return out
   finally:
     eng.close()

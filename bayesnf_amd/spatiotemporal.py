@@ -365,7 +365,7 @@ class BayesianNeuralFieldEstimator:
         compute_dtype=self.compute_dtype,
     )
 
-  def predict_samples(self, table, num_samples=1000, seed=0, group_by=None):
+  def predict_samples(self, table, num_samples=1000, seed=0, group_by=None, weights=None):
     """Joint posterior-predictive sample paths at the rows of `table`, drawn on the GPU.  Each path uses one member
     (VI: one member and one posterior draw) for all rows and adds that member's observation noise per row, so sums
     over rows carry the right spread -- what no marginal quantile of `predict` gives.
@@ -373,11 +373,14 @@ class BayesianNeuralFieldEstimator:
       group_by=column or [columns]     -> (totals, keys): totals (num_samples, G) float64, the paths summed over
         the rows of every group; keys the sorted pandas Index (MultiIndex for several columns) of the groups.  The
         group columns are any columns of `table`, feature or not.
-    The same (seed, table) gives the same numbers whatever num_samples is asked for (path s does not change)."""
+    The same (seed, table) gives the same numbers whatever num_samples is asked for (path s does not change).
+    weights (the shape of `score(...)['member_log_prob']`, e.g. `stacking_weights(...)['weights']`): a path draws its
+    member with these probabilities instead of equal ones.  None: equal weights, nothing changes."""
     if self.params_ is None:
       raise ValueError('predict_samples before fit')
     if int(num_samples) < 1:
       raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+    kw = self._weights_kw(weights)
     groups = keys = None
     if group_by is not None:
       keys, seg_offsets, seg_rows = group_rows(table, group_by)
@@ -385,8 +388,74 @@ class BayesianNeuralFieldEstimator:
     rows = self.data_handler.get_test(table)
     out = inference.sample_predictive(
         rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype)
+        ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype, **kw)
     return out if group_by is None else (out, keys)
+
+  def _weights_kw(self, weights):
+    """{} for weights=None (the callee is called as before), else the checked weights as a keyword argument."""
+    if weights is None:
+      return {}
+    inference.mixture_weights(weights, self.params_, self._ensemble_dims)      # ValueError before any GPU work
+    return {'weights': np.asarray(weights, dtype=np.float64)}
+
+  def _targets(self, what, table):
+    """The target column as float64, with the checks of `score`: NaN allowed, infinite or (count models) non-integer
+    targets refused."""
+    if self.target_col not in table.columns:
+      raise ValueError(f'{what}: the target column {self.target_col!r} is not among the columns of the table')
+    y = np.asarray(table[self.target_col].values, dtype=np.float64)
+    if np.isinf(y).any():
+      raise ValueError(f'{what}: infinite targets')
+    seen = y[np.isfinite(y)]
+    if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
+      raise ValueError(f'{what}: the {self.observation_model} observation model takes non-negative integer targets')
+    return y
+
+  def _stack(self, what, table, weights, max_iter, tol):
+    y = self._targets(what, table)
+    rows = self.data_handler.get_test(table)
+    return inference.stack_members(
+        rows, y, self.observation_model, self.params_, self._model_args(rows.shape), ensemble_dims=self._ensemble_dims,
+        weights=weights, max_iter=max_iter, tol=tol, compute_dtype=self.compute_dtype)
+
+  def stacking_weights(self, table, max_iter=10000, tol=1e-5):
+    """Stacking of the members' predictive distributions (Yao et al. 2018) on the rows of `table`, which should be
+    held out from `fit`: the simplex weights that maximise the mean log density of `table[target_col]` under the
+    weighted mixture of members, found on the GPU by EM from equal weights.  The loop stops when gap <= tol: gap bounds
+    how far 'mean_log_density' is from the best any weights reach on these rows.  NaN targets are allowed (left out);
+    the target checks are those of `score`.  -> dict:
+      'weights'                       shape of `score(table)['member_log_prob']` (VI: posterior draws are components)
+      'log_density'                   (len(table),) log density of the weighted mixture; NaN where the target is NaN,
+                                      -inf on a dropped row
+      'mean_log_density'              mean over the scored rows at 'weights'
+      'equal_weight_mean_log_density' the same at equal weights: what `score(table)['mean_log_density']` reports
+      'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
+      'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
+    The weights are taken by `predict_samples`, `predict_totals` and `score_totals` (weights=...) and scored on
+    another table by `weighted_log_density`.  Out of scope: `predict`'s marginal quantiles and `score`'s pit / crps /
+    rps stay those of the equal-weight mixture, and `fit` is unchanged."""
+    if self.params_ is None:
+      raise ValueError('stacking_weights before fit')
+    res = self._stack('stacking_weights', table, None, max_iter, tol)
+    lpd = res['log_density']
+    return {'weights': res['weights'], 'log_density': lpd, 'mean_log_density': res['objective'],
+            'equal_weight_mean_log_density': res['objective_start'], 'gap': res['gap'], 'iterations': res['iterations'],
+            'converged': res['converged'], 'n': int(np.isfinite(lpd).sum()), 'dropped': res['dropped']}
+
+  def weighted_log_density(self, table, weights):
+    """The log density of `table[target_col]` under the mixture of members with the given `weights` (the shape of
+    `score(table)['member_log_prob']`), e.g. weights learned by `stacking_weights` on another table.  -> dict:
+      'log_density' (len(table),)   NaN where the target is NaN, -inf where every weighted member gives density 0
+      'mean_log_density'            mean over the n scored rows        'n'
+    With equal weights this is `score(table)['log_density']`."""
+    if self.params_ is None:
+      raise ValueError('weighted_log_density before fit')
+    if weights is None:
+      raise ValueError('weighted_log_density: weights are required')
+    inference.mixture_weights(weights, self.params_, self._ensemble_dims)
+    res = self._stack('weighted_log_density', table, weights, 0, 0.0)
+    lpd = res['log_density']
+    return {'log_density': lpd, 'mean_log_density': res['objective'], 'n': int(np.isfinite(lpd).sum())}
 
   def score(self, table, rps=False):
     """The forecast at the rows of `table` scored against the observations `table[target_col]`, on the GPU.  NaN
@@ -432,32 +501,35 @@ class BayesianNeuralFieldEstimator:
       out['mean_rps'] = float(np.mean(out['rps'][kept], dtype=np.float64)) if kept.any() else float('nan')
     return out
 
-  def _total_summaries(self, what, table, group_by, quantiles, num_samples, seed, target=None, energy=False):
+  def _total_summaries(self, what, table, group_by, quantiles, num_samples, seed, target=None, energy=False,
+                       weights=None):
     if int(num_samples) < 1:
       raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
     if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
       raise ValueError(f'{what}: num_samples={num_samples}: the totals are summarised from at most '
                        f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    kw = self._weights_kw(weights)
     keys, seg_offsets, seg_rows = group_rows(table, group_by)
     observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
     rows = self.data_handler.get_test(table)
     out = inference.total_summaries(
         rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
         ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, quantiles=tuple(quantiles),
-        energy=bool(energy), compute_dtype=self.compute_dtype)
+        energy=bool(energy), compute_dtype=self.compute_dtype, **kw)
     return out, keys, observed
 
-  def predict_totals(self, table, group_by, quantiles=(0.5,), num_samples=1000, seed=0):
+  def predict_totals(self, table, group_by, quantiles=(0.5,), num_samples=1000, seed=0, weights=None):
     """Mean and quantile bands of the group totals of `predict_samples(table, num_samples, seed, group_by=group_by)`,
     summarised on the GPU: the (num_samples, G) matrix of totals never leaves the device.  -> (mean (G,), [one (G,) array
     per level, numpy's default 'linear' quantile of the sampled totals], keys) with keys as in `predict_samples`.
-    num_samples <= 16,384."""
+    num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
     if self.params_ is None:
       raise ValueError('predict_totals before fit')
-    out, keys, _ = self._total_summaries('predict_totals', table, group_by, quantiles, num_samples, seed)
+    out, keys, _ = self._total_summaries('predict_totals', table, group_by, quantiles, num_samples, seed, weights=weights)
     return out['mean'], [out['quantiles'][i] for i in range(out['quantiles'].shape[0])], keys
 
-  def score_totals(self, table, group_by, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0, energy=True):
+  def score_totals(self, table, group_by, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0, energy=True,
+                   weights=None):
     """The forecast of the group totals -- the sample paths of `predict_samples(table, num_samples, seed,
     group_by=group_by)` -- scored against the observed totals of `table[target_col]`, on the GPU.  -> dict:
       'keys'          the groups, as in `predict_samples`
@@ -469,7 +541,7 @@ class BayesianNeuralFieldEstimator:
       'n'             number of groups scored       'mean_crps'  mean of 'crps' over them
       'energy_score'  energy=True: the energy score of the joint paths over the scored groups, one number for the
                       whole vector of totals (num_samples^2 G / 2 differences)
-    num_samples <= 16,384."""
+    num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
     if self.params_ is None:
       raise ValueError('score_totals before fit')
     if self.target_col not in table.columns:
@@ -481,7 +553,7 @@ class BayesianNeuralFieldEstimator:
     if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
       raise ValueError(f'score_totals: the {self.observation_model} observation model takes non-negative integer targets')
     out, keys, observed = self._total_summaries(
-        'score_totals', table, group_by, quantiles, num_samples, seed, target=y, energy=energy)
+        'score_totals', table, group_by, quantiles, num_samples, seed, target=y, energy=energy, weights=weights)
     scored = ~np.isnan(observed)
     out.update(keys=keys, observed=observed, n=int(scored.sum()))
     out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')

@@ -307,6 +307,23 @@ int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux,
                               const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
                               uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out);
 
+/* The same sample paths and group totals with WEIGHTS on the members (the weights bnf_stacking_weights finds): the
+ * arguments of bnf_predictive_samples / bnf_predictive_group_sums plus
+ *   cum_weights DEVICE (n_members,) f64: the running sum of the member weights, nondecreasing, last entry 1.
+ * Path s takes the same Philox word as the equal-weight call, u = word / 2^32, and the member c_s = #{m : cum[m] <= u},
+ * clamped to n_members - 1 (found by bisection: a cum out of order can only pick another member, never an index outside
+ * loc); every draw at (s, r) then uses the counters of the equal-weight call, so weights that sit on one member give the
+ * bits of that member alone.  u moves in steps of 2^-32: a member whose weight is below 2^-32 is never drawn.
+ * cum_weights == NULL gives the bits of the unweighted call.  Run on the handle's stream, do not touch the training
+ * state, work on forward-only handles. */
+int bnf_predictive_samples_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                    const double* cum_weights, float* out);
+int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                       const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
+                                       int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                       const double* cum_weights, void* work, size_t work_bytes, double* out);
+
 /* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
  * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
  * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
@@ -350,6 +367,46 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
 #define BNF_RPS_MAX_MEMBERS 2048
 int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
                   const float* y, float* rps);
+
+/* The matrix of per-member LOG DENSITIES of held-out observations: out DEVICE (n_members, n_rows) f32,
+ * out[m][r] = log p_m(y_r), the f32 terms whose sums over r bnf_predictive_scores reports as member_ll (the forms of the
+ * training loss, bnf_scoring.h).  loc, aux, y as for bnf_predictive_scores.  Every member of a row whose y is NaN or
+ * infinite gets NaN; -inf is a legal value (a density of 0).  Runs on the handle's stream, does not touch the training
+ * state, works on forward-only handles. */
+int bnf_member_log_density(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                           const float* y, float* out);
+
+/* STACKING of predictive distributions (Yao et al. 2018): simplex weights w over the members that maximise the held-out
+ * log score f(w) = (1 / n) sum_r log sum_m w_m exp(logdens[m][r]), by EM on the mixture weights:
+ *   g_m = (1 / n) sum_r exp(logdens[m][r] - lse_r),  lse_r = log sum_m w_m exp(logdens[m][r]),  w_m <- w_m g_m
+ * (renormalised), which never lowers f.  f is concave and g its gradient, so gap = max_m g_m - 1 >= f(w*) - f(w) for the
+ * optimum w*: the loop stops as soon as gap <= tol, or after max_iter updates, and reports the gap it stopped at -- a
+ * bound on the distance to the optimum that needs no reference optimiser.
+ *   logdens DEVICE (n_members, n_rows) f32 as bnf_member_log_density writes it.  A row holding a NaN is left out (not
+ *     scored, not counted).  A row without a NaN is SCORED when lse_r is finite and DROPPED otherwise (every member with
+ *     w_m > 0 at -inf): dropped rows are left out of every sum and counted.  n = the scored rows.
+ *   w_init DEVICE (n_members,) f64 the starting weights, or NULL = uniform.  A weight of 0 stays 0.
+ *   max_iter = 0: a pure evaluation of w_init (weights learned on one table scored on another).
+ *   weights DEVICE (n_members,) f64: the result; for max_iter = 0 the bits of w_init.
+ *   lpd DEVICE (n_rows,) f32 or NULL: (float) lse_r at the returned weights; NaN rows NaN, dropped rows -inf.
+ *   info DEVICE (5,) f64, all evaluated at the weights that are returned: [0] f, [1] f at the starting weights, [2] gap,
+ *     [3] updates done, [4] rows dropped.  Converged: info[2] <= tol.  No scored row: weights = the starting weights,
+ *     [0], [1], [2] NaN, [3] = 0.
+ *   work DEVICE, work_bytes: 8 * (BNF_STACK_STATE_DOUBLES + (n_members + 3) * ceil(n_rows / BNF_STACK_ROW_TILE)) bytes
+ *     (the stop flag, the per-tile sums of every member, of lse and of the row counts); BNF_ERR_INVALID below that, and
+ *     for n_members < 1, n_rows < 1, max_iter < 0, tol negative or NaN.
+ * Everything after logdens is f64, exp and log included; every sum is in an order the shapes fix (no floating-point
+ * atomics): two calls give the same bits.  An iteration is two kernels; they are enqueued BNF_STACK_BATCH iterations at a
+ * time and return at once when the stop flag is set.  The call SYNCHRONISES on the handle's stream once per batch to read
+ * that flag (beside bnf_profile_read the one entry point that waits for the device).  Runs
+ * on the handle's stream, does not touch the training state, works on forward-only handles; the observation model of the
+ * handle plays no part. */
+#define BNF_STACK_ROW_TILE 1024
+#define BNF_STACK_STATE_DOUBLES 8
+#define BNF_STACK_BATCH 64
+int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members, int64_t n_rows, const double* w_init,
+                         int64_t max_iter, double tol, void* work, size_t work_bytes, double* weights, float* lpd,
+                         double* info);
 
 /* SUMMARIES of an ensemble of sample paths, column by column: x DEVICE (n_samples, n_cols) f64 row-major -- the layout
  * bnf_predictive_group_sums writes, one column per group total -- and optionally the observed totals y DEVICE (n_cols,)
