@@ -51,7 +51,8 @@ EXPORTS = (
     'bnf_normal_mixture_quantiles', 'bnf_count_mixture_quantiles', 'bnf_predictive_samples', 'bnf_predictive_group_sums',
     'bnf_predictive_scores', 'bnf_count_rps', 'bnf_sample_summaries', 'bnf_sample_energy_score',
     'bnf_member_log_density', 'bnf_stacking_weights', 'bnf_predictive_samples_weighted',
-    'bnf_predictive_group_sums_weighted',
+    'bnf_predictive_group_sums_weighted', 'bnf_normal_mixture_quantiles_weighted',
+    'bnf_count_mixture_quantiles_weighted', 'bnf_predictive_scores_weighted', 'bnf_count_rps_weighted',
     'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
@@ -153,6 +154,10 @@ def load():
   lib.bnf_predictive_samples_weighted.argtypes = [vp, vp, vp, i64, i64, i64, C.c_uint64, i64, i64, vp, vp]
   lib.bnf_predictive_group_sums_weighted.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp,
                                                      C.c_size_t, vp]
+  lib.bnf_normal_mixture_quantiles_weighted.argtypes = [vp, vp, vp, vp, i64, i64, C.POINTER(C.c_float), i32, i32, vp]
+  lib.bnf_count_mixture_quantiles_weighted.argtypes = [vp, vp, vp, vp, i64, i64, C.POINTER(C.c_float), i32, vp, vp]
+  lib.bnf_predictive_scores_weighted.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, C.c_size_t, vp, vp, vp]
+  lib.bnf_count_rps_weighted.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_debug_loss_and_grad.argtypes = [vp, i64, i64, vp, vp]
   lib.bnf_debug_row_index.argtypes = [vp, i64, i64, vp]
   lib.bnf_debug_vi_eps.argtypes = [vp, i64, vp]

@@ -1393,10 +1393,11 @@ static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const 
                      seg_offsets, (int32_t)G, R, S, partial, out);
 }
 
-// held-out scoring launches (bnf_scoring.h), one instantiation per observation model
-template <int OBS>
-static void launch_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, const float* y,
-                                     double* ll_partial, double* pair_partial, int64_t n_slots, double* member_ll,
+// held-out scoring launches (bnf_scoring.h), one instantiation per observation model and for the member weights wts
+// (WEIGHTED: wts non-null, no member_ll)
+template <int OBS, bool WEIGHTED>
+static void launch_predictive_scores(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t M,
+                                     int64_t R, const float* y, double* ll_partial, double* pair_partial, int64_t n_slots, double* member_ll,
                                      float* lpd, float* pit, float* crps) {
   const int64_t nt = cdiv(R, kScoreTile);
   if (member_ll) {
@@ -1406,24 +1407,24 @@ static void launch_predictive_scores(bnf_handle* h, const float* loc, const floa
                        member_ll);
   }
   if (crps)
-    hipLaunchKernelGGL(k_score_crps_pairs, dim3((unsigned)nt, (unsigned)n_slots), dim3(256), 0, h->stream, loc, aux,
-                       (int32_t)M, R, pair_partial);
+    hipLaunchKernelGGL((k_score_crps_pairs<WEIGHTED>), dim3((unsigned)nt, (unsigned)n_slots), dim3(256), 0, h->stream, loc,
+                       aux, wts, (int32_t)M, R, pair_partial);
   if (lpd || crps || (pit && OBS == BNF_OBS_NORMAL))
-    hipLaunchKernelGGL((k_score_rows<OBS>), dim3(cdiv(R, 64)), dim3(64), 0, h->stream, loc, aux, (int32_t)M, R, y,
+    hipLaunchKernelGGL((k_score_rows<OBS, WEIGHTED>), dim3(cdiv(R, 64)), dim3(64), 0, h->stream, loc, aux, wts, (int32_t)M, R, y,
                        pair_partial, (int32_t)n_slots, lpd, pit, crps);
   if (pit && OBS != BNF_OBS_NORMAL)
-    hipLaunchKernelGGL(k_score_count_pit, dim3(cdiv(R, 64), 2), dim3(64), 0, h->stream, loc, aux, (int32_t)M, R,
+    hipLaunchKernelGGL((k_score_count_pit<WEIGHTED>), dim3(cdiv(R, 64), 2), dim3(64), 0, h->stream, loc, aux, wts, (int32_t)M, R,
                        (int32_t)OBS, y, pit);
 }
 
 // ranked probability score (bnf_rps.h): one wave per row, the rows beyond 2^20 blocks by grid stride
-template <int OBS>
-static void launch_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, const float* y,
-                             float* rps) {
+template <int OBS, bool WEIGHTED>
+static void launch_count_rps(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t M, int64_t R,
+                             const float* y, float* rps) {
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_count_rps<OBS>, (int)rps_lds_bytes(BNF_RPS_MAX_MEMBERS), &attr_done);
-  hipLaunchKernelGGL((k_count_rps<OBS>), dim3((unsigned)std::min<int64_t>(R, 1 << 20)), dim3(64), rps_lds_bytes(M),
-                     h->stream, loc, aux, (int32_t)M, R, y, rps);
+  allow_lds(h, &k_count_rps<OBS, WEIGHTED>, (int)rps_lds_bytes(BNF_RPS_MAX_MEMBERS), &attr_done);
+  hipLaunchKernelGGL((k_count_rps<OBS, WEIGHTED>), dim3((unsigned)std::min<int64_t>(R, 1 << 20)), dim3(64), rps_lds_bytes(M),
+                     h->stream, loc, aux, wts, (int32_t)M, R, y, rps);
 }
 
 // summaries of sample paths (bnf_totals.h): one workgroup per slab of C adjacent columns, C * P <= 16,384 doubles of LDS
@@ -1944,9 +1945,10 @@ int bnf_forward(bnf_handle* h, const float* theta, int64_t n_members, const floa
   return BNF_OK;
 }
 
-int bnf_normal_mixture_quantiles(bnf_handle* h, const float* means, const float* scales,
-                                 int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                 int32_t approximate, float* out) {
+// wts: the member weights of the *_weighted entry points, DEVICE (n_members,) f64; NULL = the equal-weight kernels
+static int normal_mixture_quantiles_impl(bnf_handle* h, const float* means, const float* scales, const double* wts,
+                                         int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                         int32_t approximate, float* out) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
   if (!means || !scales || !q || !out || n_members < 1 || n_rows < 1 || n_q < 0)
     return fail(BNF_ERR_INVALID, "argument");
@@ -1963,20 +1965,30 @@ int bnf_normal_mixture_quantiles(bnf_handle* h, const float* means, const float*
     hipLaunchKernelGGL(k_bracket, dim3(1), dim3(64), 0, h->stream, mpart, nb_m, spart, nb_s, bracket);
   }
   for (int i = 0; i < n_q; ++i) {
-    if (approximate)
-      hipLaunchKernelGGL(k_quantile_approx, dim3(cdiv(n_rows, 256)), dim3(256), 0, h->stream, means,
-                         scales, n_members, n_rows, q[i], out + (int64_t)i * n_rows);
+    float* o = out + (int64_t)i * n_rows;
+    const dim3 grid(cdiv(n_rows, 256));
+    if (approximate && wts)
+      hipLaunchKernelGGL(k_quantile_approx<true>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, q[i], o);
+    else if (approximate)
+      hipLaunchKernelGGL(k_quantile_approx<false>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, q[i], o);
+    else if (wts)
+      hipLaunchKernelGGL(k_quantile_root<true>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, bracket, q[i], o);
     else
-      hipLaunchKernelGGL(k_quantile_root, dim3(cdiv(n_rows, 256)), dim3(256), 0, h->stream, means,
-                         scales, n_members, n_rows, bracket, q[i], out + (int64_t)i * n_rows);
+      hipLaunchKernelGGL(k_quantile_root<false>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, bracket, q[i], o);
   }
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
 
-int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* aux,
-                                int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                float* means, float* out) {
+int bnf_normal_mixture_quantiles(bnf_handle* h, const float* means, const float* scales,
+                                 int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                 int32_t approximate, float* out) {
+  return normal_mixture_quantiles_impl(h, means, scales, nullptr, n_members, n_rows, q, n_q, approximate, out);
+}
+
+static int count_mixture_quantiles_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts,
+                                        int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                        float* means, float* out) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
   if (h->cfg.obs_model != BNF_OBS_NB && h->cfg.obs_model != BNF_OBS_ZINB)
     return fail(BNF_ERR_STATE, "handle's observation model is not NB / ZINB");
@@ -1991,11 +2003,22 @@ int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* au
   hipLaunchKernelGGL(k_count_moments, dim3(nb), dim3(256), 0, h->stream, loc, aux, n_members, n_rows,
                      h->cfg.obs_model, means, part);
   hipLaunchKernelGGL(k_count_bracket, dim3(1), dim3(64), 0, h->stream, part, nb, bracket);
-  for (int i = 0; i < n_q; ++i)
-    hipLaunchKernelGGL(k_count_quantile_root, dim3(cdiv(n_rows, 64)), dim3(64), 0, h->stream, loc, aux,
-                       n_members, n_rows, h->cfg.obs_model, bracket, q[i], out + (int64_t)i * n_rows);
+  for (int i = 0; i < n_q; ++i) {
+    if (wts)
+      hipLaunchKernelGGL(k_count_quantile_root<true>, dim3(cdiv(n_rows, 64)), dim3(64), 0, h->stream, loc, aux, wts,
+                         n_members, n_rows, h->cfg.obs_model, bracket, q[i], out + (int64_t)i * n_rows);
+    else
+      hipLaunchKernelGGL(k_count_quantile_root<false>, dim3(cdiv(n_rows, 64)), dim3(64), 0, h->stream, loc, aux, wts,
+                         n_members, n_rows, h->cfg.obs_model, bracket, q[i], out + (int64_t)i * n_rows);
+  }
   HIPCHK(hipGetLastError());
   return BNF_OK;
+}
+
+int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* aux,
+                                int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                float* means, float* out) {
+  return count_mixture_quantiles_impl(h, loc, aux, nullptr, n_members, n_rows, q, n_q, means, out);
 }
 
 
@@ -2090,9 +2113,9 @@ int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const fl
 }
 
 // ---- held-out scoring (bnf_scoring.h) ---------------------------------------------
-int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                          const float* y, void* work, size_t work_bytes, double* member_ll, float* lpd, float* pit,
-                          float* crps) {
+static int predictive_scores_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t n_members,
+                                  int64_t n_rows, const float* y, void* work, size_t work_bytes, double* member_ll,
+                                  float* lpd, float* pit, float* crps) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
   if (!loc || !aux || !y || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
     return fail(BNF_ERR_INVALID, "argument");
@@ -2110,13 +2133,27 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
   HIPCHK(hipSetDevice(h->cfg.device));
   double* ll_partial = (double*)work;
   double* pair_partial = (double*)((char*)work + ll_bytes);
-  switch (h->cfg.obs_model) {
-    case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-    case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-    default: launch_predictive_scores<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+  if (wts) {
+    switch (h->cfg.obs_model) {
+      case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+      case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+      default: launch_predictive_scores<BNF_OBS_ZINB, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+    }
+  } else {
+    switch (h->cfg.obs_model) {
+      case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+      case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+      default: launch_predictive_scores<BNF_OBS_ZINB, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
+    }
   }
   HIPCHK(hipGetLastError());
   return BNF_OK;
+}
+
+int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                          const float* y, void* work, size_t work_bytes, double* member_ll, float* lpd, float* pit,
+                          float* crps) {
+  return predictive_scores_impl(h, loc, aux, nullptr, n_members, n_rows, y, work, work_bytes, member_ll, lpd, pit, crps);
 }
 
 // ---- stacking of the members on held-out rows (bnf_stacking.h) ----------------------
@@ -2183,8 +2220,8 @@ int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members,
 }
 
 // ---- ranked probability score of count forecasts (bnf_rps.h) -----------------------
-int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows, const float* y,
-                  float* rps) {
+static int count_rps_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t n_members,
+                          int64_t n_rows, const float* y, float* rps) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
   if (!loc || !aux || !y || !rps || n_members < 1 || n_rows < 1 || n_rows > 0x7fffffffLL)
     return fail(BNF_ERR_INVALID, "argument");
@@ -2194,10 +2231,52 @@ int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_m
   if (h->cfg.obs_model == BNF_OBS_NORMAL)
     return fail(BNF_ERR_INVALID, "rps: count observation models only (NORMAL: the crps of bnf_predictive_scores)");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->cfg.obs_model == BNF_OBS_NB) launch_count_rps<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, y, rps);
-  else launch_count_rps<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, y, rps);
+  const bool nb = h->cfg.obs_model == BNF_OBS_NB;
+  if (wts && nb) launch_count_rps<BNF_OBS_NB, true>(h, loc, aux, wts, n_members, n_rows, y, rps);
+  else if (wts) launch_count_rps<BNF_OBS_ZINB, true>(h, loc, aux, wts, n_members, n_rows, y, rps);
+  else if (nb) launch_count_rps<BNF_OBS_NB, false>(h, loc, aux, wts, n_members, n_rows, y, rps);
+  else launch_count_rps<BNF_OBS_ZINB, false>(h, loc, aux, wts, n_members, n_rows, y, rps);
   HIPCHK(hipGetLastError());
   return BNF_OK;
+}
+
+int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows, const float* y,
+                  float* rps) {
+  return count_rps_impl(h, loc, aux, nullptr, n_members, n_rows, y, rps);
+}
+
+// ---- the marginal forecast of the WEIGHTED mixture: quantiles, scores and the RPS with member weights ------------------
+// weights DEVICE (n_members,) f64 as bnf_stacking_weights writes them; NULL is BNF_ERR_INVALID (the unweighted calls have
+// their own names).  Not validated: reading them would cost a sync.
+int bnf_normal_mixture_quantiles_weighted(bnf_handle* h, const float* means, const float* scales, const double* weights,
+                                          int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                          int32_t approximate, float* out) {
+  if (const int rc = no_device()) return rc;
+  if (!weights) return fail(BNF_ERR_INVALID, "weights");
+  return normal_mixture_quantiles_impl(h, means, scales, weights, n_members, n_rows, q, n_q, approximate, out);
+}
+
+int bnf_count_mixture_quantiles_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
+                                         int64_t n_members, int64_t n_rows, const float* q, int32_t n_q, float* means,
+                                         float* out) {
+  if (const int rc = no_device()) return rc;
+  if (!weights) return fail(BNF_ERR_INVALID, "weights");
+  return count_mixture_quantiles_impl(h, loc, aux, weights, n_members, n_rows, q, n_q, means, out);
+}
+
+int bnf_predictive_scores_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
+                                   int64_t n_members, int64_t n_rows, const float* y, void* work, size_t work_bytes,
+                                   float* lpd, float* pit, float* crps) {
+  if (const int rc = no_device()) return rc;
+  if (!weights) return fail(BNF_ERR_INVALID, "weights");
+  return predictive_scores_impl(h, loc, aux, weights, n_members, n_rows, y, work, work_bytes, nullptr, lpd, pit, crps);
+}
+
+int bnf_count_rps_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights, int64_t n_members,
+                           int64_t n_rows, const float* y, float* rps) {
+  if (const int rc = no_device()) return rc;
+  if (!weights) return fail(BNF_ERR_INVALID, "weights");
+  return count_rps_impl(h, loc, aux, weights, n_members, n_rows, y, rps);
 }
 
 // ---- summaries and scores of sample paths (bnf_totals.h) -----------------------------

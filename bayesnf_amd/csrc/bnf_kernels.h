@@ -1174,18 +1174,30 @@ __global__ void k_bracket(const float* mean_part, int n_mean_part, const float* 
 
 __device__ __forceinline__ float ndtrf(float z) { return 0.5f * erfcf(-z * 0.70710678118654752440f); }
 
+// Member weights (the *_weighted entry points): WEIGHTED is a template parameter of the kernels below and `wts`
+// (n_members,) f64 is read only under it, so the unweighted instantiation is the arithmetic it was without it.  The
+// weighted sums are f64: w_m times the f32 term, members in order.
+template <bool WEIGHTED>
 __device__ __forceinline__ float mix_cdf(const float* __restrict__ means,
-                                         const float* __restrict__ scales, int64_t n_members,
-                                         int64_t n_rows, int64_t r, float x) {
-  float acc = 0.f;
-  for (int64_t m = 0; m < n_members; ++m) acc += ndtrf((x - means[m * n_rows + r]) / scales[m]);
-  return acc / (float)n_members;
+                                         const float* __restrict__ scales, const double* __restrict__ wts,
+                                         int64_t n_members, int64_t n_rows, int64_t r, float x) {
+  if constexpr (WEIGHTED) {
+    double acc = 0.0;
+    for (int64_t m = 0; m < n_members; ++m) acc += wts[m] * (double)ndtrf((x - means[m * n_rows + r]) / scales[m]);
+    return (float)acc;
+  } else {
+    float acc = 0.f;
+    for (int64_t m = 0; m < n_members; ++m) acc += ndtrf((x - means[m * n_rows + r]) / scales[m]);
+    return acc / (float)n_members;
+  }
 }
 
 // Chandrupatla's bracketing root finder (the algorithm behind
 // tfp.math.find_root_chandrupatla), one thread per row.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_quantile_root(const float* __restrict__ means,
                                                        const float* __restrict__ scales,
+                                                       const double* __restrict__ wts,
                                                        int64_t n_members, int64_t n_rows,
                                                        const float* __restrict__ bracket, float q,
                                                        float* __restrict__ out) {
@@ -1193,14 +1205,14 @@ __global__ __launch_bounds__(256) void k_quantile_root(const float* __restrict__
   if (r >= n_rows) return;
   const float vtol = 1e-5f, ptol = 1e-8f;
   float a = bracket[0], b = bracket[1];
-  float fa = mix_cdf(means, scales, n_members, n_rows, r, a) - q;
-  float fb = mix_cdf(means, scales, n_members, n_rows, r, b) - q;
+  float fa = mix_cdf<WEIGHTED>(means, scales, wts, n_members, n_rows, r, a) - q;
+  float fb = mix_cdf<WEIGHTED>(means, scales, wts, n_members, n_rows, r, b) - q;
   float c = a, fc = fa, t = 0.5f;
   float best = fabsf(fa) < fabsf(fb) ? a : b;
   float fbest = fabsf(fa) < fabsf(fb) ? fa : fb;
   for (int it = 0; it < 60 && fabsf(fbest) > vtol; ++it) {
     const float xn = a + t * (b - a);
-    const float fn = mix_cdf(means, scales, n_members, n_rows, r, xn) - q;
+    const float fn = mix_cdf<WEIGHTED>(means, scales, wts, n_members, n_rows, r, xn) - q;
     const bool same = (fn > 0.f) == (fa > 0.f) && (fn < 0.f) == (fa < 0.f);
     if (same) { c = a; fc = fa; }
     else { c = b; fc = fb; b = a; fb = fa; }
@@ -1221,12 +1233,24 @@ __global__ __launch_bounds__(256) void k_quantile_root(const float* __restrict__
 }
 
 // moment-matched Normal quantile (inference.py:55-84)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_quantile_approx(const float* __restrict__ means,
                                                          const float* __restrict__ scales,
+                                                         const double* __restrict__ wts,
                                                          int64_t n_members, int64_t n_rows, float q,
                                                          float* __restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rows) return;
+  if constexpr (WEIGHTED) {                    // mean = sum w mu, var = sum w (sd^2 + mu^2) - mean^2, all of it f64: the
+    double s1 = 0.0, s2 = 0.0;                 // difference cancels (one member of weight 1: to sd^2 out of sd^2 + mu^2)
+    for (int64_t m = 0; m < n_members; ++m) {
+      const double mu = means[m * n_rows + r], sd = scales[m], w = wts[m];
+      s1 += w * mu;
+      s2 += w * (sd * sd + mu * mu);
+    }
+    out[r] = (float)(s1 + sqrt(fmax(s2 - s1 * s1, 0.0)) * normcdfinv((double)q));
+    return;
+  }
   float s1 = 0.f, s2 = 0.f;
   for (int64_t m = 0; m < n_members; ++m) {
     const float mu = means[m * n_rows + r], sd = scales[m];
@@ -1329,10 +1353,11 @@ __device__ inline double betainc_xc(double a, double b, double x, double xc) {
   return 1.0 - exp(lnpre) * beta_cf(b, a, xc) / b;
 }
 
-// mean over members of the (ZI)NB cdf at x >= 0, row r
+// mean over members (WEIGHTED: sum of wts[e] times) of the (ZI)NB cdf at x >= 0, row r
+template <bool WEIGHTED>
 __device__ inline float count_mix_cdf(const float* __restrict__ loc, const float* __restrict__ aux,
-                                      int64_t n_members, int64_t n_rows, int32_t obs, int64_t r,
-                                      float x) {
+                                      const double* __restrict__ wts, int64_t n_members, int64_t n_rows,
+                                      int32_t obs, int64_t r, float x) {
   double acc = 0.0;
   for (int64_t e = 0; e < n_members; ++e) {
     const double s = aux[e * 3 + 1];
@@ -1342,15 +1367,19 @@ __device__ inline float count_mix_cdf(const float* __restrict__ loc, const float
       const double pi = aux[e * 3 + 2];
       F = pi + (1.0 - pi) * F;
     }
-    acc += F;
+    if constexpr (WEIGHTED) acc += wts[e] * F;
+    else acc += F;
   }
-  return (float)(acc / (double)n_members);
+  if constexpr (WEIGHTED) return (float)acc;
+  else return (float)(acc / (double)n_members);
 }
 
 // one thread per row: Chandrupatla on [0, max mean + 1.1 rsqrt(1-q) max sd], then ceil;
 // rows whose mixture pmf(0) already exceeds q are 0 (inference.py:319-333).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(64) void k_count_quantile_root(const float* __restrict__ loc,
                                                             const float* __restrict__ aux,
+                                                            const double* __restrict__ wts,
                                                             int64_t n_members, int64_t n_rows,
                                                             int32_t obs,
                                                             const float* __restrict__ bracket, float q,
@@ -1359,15 +1388,15 @@ __global__ __launch_bounds__(64) void k_count_quantile_root(const float* __restr
   if (r >= n_rows) return;
   const float vtol = 1e-5f, ptol = 1e-8f;
   float a = 0.f, b = bracket[2] + 1.1f * rsqrtf(1.0f - q) * bracket[3];
-  float fa = count_mix_cdf(loc, aux, n_members, n_rows, obs, r, a) - q;
+  float fa = count_mix_cdf<WEIGHTED>(loc, aux, wts, n_members, n_rows, obs, r, a) - q;
   if (fa > 0.f) { out[r] = 0.f; return; }
-  float fb = count_mix_cdf(loc, aux, n_members, n_rows, obs, r, b) - q;
+  float fb = count_mix_cdf<WEIGHTED>(loc, aux, wts, n_members, n_rows, obs, r, b) - q;
   float c = a, fc = fa, t = 0.5f;
   float best = fabsf(fa) < fabsf(fb) ? a : b;
   float fbest = fabsf(fa) < fabsf(fb) ? fa : fb;
   for (int it = 0; it < 60 && fabsf(fbest) > vtol; ++it) {
     const float xn = a + t * (b - a);
-    const float fn = count_mix_cdf(loc, aux, n_members, n_rows, obs, r, xn) - q;
+    const float fn = count_mix_cdf<WEIGHTED>(loc, aux, wts, n_members, n_rows, obs, r, xn) - q;
     const bool same = (fn > 0.f) == (fa > 0.f) && (fn < 0.f) == (fa < 0.f);
     if (same) { c = a; fc = fa; }
     else { c = b; fc = fb; b = a; fb = fa; }

@@ -32,6 +32,14 @@
 //   total_count 0.05) would need 3e8 terms; a strided or quadrature form for such rows is out of scope here.
 //   A member whose parameters are not finite, or whose mean is 0 or beyond 2^52, gives NaN as well.
 //
+// Member weights (bnf_count_rps_weighted, WEIGHTED below): F_r = sum_m w_m F_{m,r} and P0 = sum_m w_m aux[m][2], w on
+//   the simplex.  Window, eps and cap are the same, and so is the truncation argument: outside [a_r, b_r) every member's
+//   tail is below eps, and a weighted mean of tails that are each below eps is below eps; past b_r it still falls with the
+//   largest ratio among the members.  The weights are not read by the library's host side: weights off the simplex give a
+//   meaningless score, never an access outside loc / aux / wts.  A member of weight exactly 0 adds nothing to F but still
+//   widens the window (and can cap the row), and a NaN in its parameters still gives NaN: the Python layer drops such
+//   members before the call.  w_m multiplies F_{m,r}(k) where lane j adds the members of one k, in member order.
+//
 // Arithmetic: softplus in f32 (as count_mix_cdf), everything after it f64.  Every sum is in an order the shapes fix (members
 // in order inside a tile column, member chunks in order, k over lanes then the wave butterfly): no floating-point atomics,
 // two calls give the same bits.
@@ -71,9 +79,10 @@ __device__ __forceinline__ double wave_min_f64(double v) {
   return v;
 }
 
-template <int OBS>
+template <int OBS, bool WEIGHTED>
 __global__ __launch_bounds__(64) __attribute__((flatten)) void k_count_rps(const float* __restrict__ loc,
-                                                                           const float* __restrict__ aux, int32_t M, int64_t R,
+                                                                           const float* __restrict__ aux,
+                                                                           const double* __restrict__ wts, int32_t M, int64_t R,
                                                                            const float* __restrict__ y,
                                                                            float* __restrict__ rps) {
   extern __shared__ __attribute__((aligned(16))) double rps_sm[];
@@ -93,8 +102,12 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_count_rps(const
   double p0 = 0.0;                                    // mean zero inflation: the same for every row and lane -- M <= 2,048
                                                       // cached loads per block, members in order (as the restatement adds them)
   if constexpr (OBS == BNF_OBS_ZINB) {
-    for (int32_t m = 0; m < M; ++m) p0 += (double)aux[m * 3 + 2];
-    p0 /= (double)M;
+    if constexpr (WEIGHTED) {
+      for (int32_t m = 0; m < M; ++m) p0 += wts[m] * (double)aux[m * 3 + 2];
+    } else {
+      for (int32_t m = 0; m < M; ++m) p0 += (double)aux[m * 3 + 2];
+      p0 /= (double)M;
+    }
   }
 
   for (int64_t r = blockIdx.x; r < R; r += gridDim.x) {
@@ -175,10 +188,13 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_count_rps(const
         }
         __syncthreads();
 #pragma unroll 8
-        for (int32_t i = 0; i < n; ++i) acc += tile[lane * kRpsPitch + i];
+        for (int32_t i = 0; i < n; ++i) {
+          if constexpr (WEIGHTED) acc += wts[c * 64 + i] * tile[lane * kRpsPitch + i];
+          else acc += tile[lane * kRpsPitch + i];
+        }
         __syncthreads();                               // the next chunk overwrites the tile
       }
-      const double d = acc / dM - (k0 + (double)lane >= yd ? 1.0 : 0.0);
+      const double d = (WEIGHTED ? acc : acc / dM) - (k0 + (double)lane >= yd ? 1.0 : 0.0);
       total += d * d;
       all_done = __ballot(!done) == 0ull;
       k0 = kn;

@@ -12,6 +12,11 @@
 //   crps (R,) f32        NORMAL: (1 / M) sum_i A(y - mu_i, s_i) - (1 / (2 M^2)) sum_ij A(mu_i - mu_j, sqrt(s_i^2 + s_j^2)),
 //                        A(m, s) = m (2 Phi(m / s) - 1) + 2 s phi(m / s)                       (Grimit et al. 2006)
 // A row whose y is not finite gives NaN in every per-row output and adds nothing to member_ll.
+// bnf_predictive_scores_weighted (WEIGHTED below), w (M,) f64 on the simplex, the forecast sum_m w_m p_m:
+//   lpd   log sum_m w_m p_m(y_r);   pit   sum_m w_m F_m on either side of y_r
+//   crps  sum_i w_i A(y - mu_i, s_i) - [sum_{j<i} w_i w_j A(mu_i - mu_j, sqrt(s_i^2 + s_j^2)) + sum_i w_i^2 s_i / sqrt(pi)]
+//   Each f32 term is converted to double and multiplied by w_m there.  The weights are not validated (reading them would
+//   cost a sync): weights off the simplex give meaningless numbers, never an access outside loc / aux / wts.
 //
 // Arithmetic: every per-(member, row) term is f32; every sum over members, over member pairs and over rows is f64, in an
 // order that depends on the shapes alone (no floating-point atomics): two calls give the same bits.
@@ -148,16 +153,21 @@ __global__ __launch_bounds__(256) void k_score_member_ll_combine(const double* _
 // partial (gridDim.y, R) f64: block (x, p) writes the sum of its slots' pairs for the rows of tile x, always.
 // Bound by the VALU: erff + expf + the rest are ~40 vector instructions per evaluation against 4 bytes loaded per 8.
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool FULL>
-__device__ __forceinline__ void score_pairs_chunk(const float* __restrict__ loc, const float* __restrict__ aux, int64_t R,
+// WEIGHTED (bnf_predictive_scores_weighted): the sum of w_i w_j A(...).  wts (M,) f64 is read at the indices aux is read
+// at; w_i w_j is the same in every lane and is formed once per pair next to c1, c2 (one v_mul_f64 per evaluation more).
+template <bool FULL, bool WEIGHTED>
+__device__ __forceinline__ void score_pairs_chunk(const float* __restrict__ loc, const float* __restrict__ aux,
+                                                  const double* __restrict__ wts, int64_t R,
                                                   const int64_t (&row)[kScoreRowsPerThread], int32_t i0, int32_t ni,
                                                   double (&acc)[kScoreRowsPerThread]) {
   float mui[kScoreChunk][kScoreRowsPerThread], vi[kScoreChunk];
+  double wi[WEIGHTED ? kScoreChunk : 1];
 #pragma unroll
   for (int ii = 0; ii < kScoreChunk; ++ii) {
     const int32_t i = (FULL || ii < ni) ? i0 + ii : i0;      // a short last chunk repeats its first member, unused
     const float s = aux[i * 3];
     vi[ii] = s * s;
+    if constexpr (WEIGHTED) wi[ii] = wts[i];
 #pragma unroll
     for (int k = 0; k < kScoreRowsPerThread; ++k) mui[ii][k] = loc[(int64_t)i * R + row[k]];
   }
@@ -170,6 +180,8 @@ __device__ __forceinline__ void score_pairs_chunk(const float* __restrict__ loc,
   for (int32_t j = 0; j < j_end; ++j) {
     const float sj = aux[j * 3];
     const float vj = sj * sj;
+    double wj = 0.0;
+    if constexpr (WEIGHTED) wj = wts[j];
     float cur[kScoreRowsPerThread];
     const int32_t jn = j + 1 < j_end ? j + 1 : j;
 #pragma unroll
@@ -180,15 +192,23 @@ __device__ __forceinline__ void score_pairs_chunk(const float* __restrict__ loc,
         const float s2 = vi[ii] + vj;
         const float rs = rsqrtf(s2);
         const float c1 = rs * 0.70710678118654752440f, c2 = (s2 * rs) * 0.79788456080286535588f;
+        if constexpr (WEIGHTED) {
+          const double ww = wi[ii] * wj;
 #pragma unroll
-        for (int k = 0; k < kScoreRowsPerThread; ++k) acc[k] += (double)score_abs_moment(mui[ii][k] - cur[k], c1, c2);
+          for (int k = 0; k < kScoreRowsPerThread; ++k) acc[k] += ww * (double)score_abs_moment(mui[ii][k] - cur[k], c1, c2);
+        } else {
+#pragma unroll
+          for (int k = 0; k < kScoreRowsPerThread; ++k) acc[k] += (double)score_abs_moment(mui[ii][k] - cur[k], c1, c2);
+        }
       }
     }
   }
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_score_crps_pairs(const float* __restrict__ loc, const float* __restrict__ aux,
-                                                          int32_t M, int64_t R, double* __restrict__ partial) {
+                                                          const double* __restrict__ wts, int32_t M, int64_t R,
+                                                          double* __restrict__ partial) {
   const int64_t base = (int64_t)blockIdx.x * kScoreTile + threadIdx.x;
   int64_t row[kScoreRowsPerThread];
 #pragma unroll
@@ -203,8 +223,8 @@ __global__ __launch_bounds__(256) void k_score_crps_pairs(const float* __restric
       if (half == 1 && c == q) break;                         // an odd number of chunks: the middle one once
       const int32_t i0 = c * kScoreChunk;
       const int32_t ni = M - i0 < kScoreChunk ? M - i0 : kScoreChunk;
-      if (ni == kScoreChunk) score_pairs_chunk<true>(loc, aux, R, row, i0, ni, acc);
-      else score_pairs_chunk<false>(loc, aux, R, row, i0, ni, acc);
+      if (ni == kScoreChunk) score_pairs_chunk<true, WEIGHTED>(loc, aux, wts, R, row, i0, ni, acc);
+      else score_pairs_chunk<false, WEIGHTED>(loc, aux, wts, R, row, i0, ni, acc);
     }
   }
 #pragma unroll
@@ -218,9 +238,12 @@ __global__ __launch_bounds__(256) void k_score_crps_pairs(const float* __restric
 //         member's log density is -- also where every density underflows
 //   pit   NORMAL: the mean of ndtrf, both rows (counts: k_score_count_pit)
 //   crps  first term here, pair sum from k_score_crps_pairs' partials (added in slot order), diagonal sum_i s_i / sqrt(pi)
+// WEIGHTED: every term of the three sums times w_m (the diagonal: w_m^2) in f64, and no division by M at the end:
+//   lpd = mx + log sum_m w_m exp(lp_m - mx), pit = sum_m w_m Phi, crps = sum w A - (pairs + sum w^2 s / sqrt(pi)).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int OBS>
-__global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc, const float* __restrict__ aux, int32_t M,
+template <int OBS, bool WEIGHTED>
+__global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc, const float* __restrict__ aux,
+                                                   const double* __restrict__ wts, int32_t M,
                                                    int64_t R, const float* __restrict__ y,
                                                    const double* __restrict__ pair_partial, int32_t n_partial,
                                                    float* __restrict__ lpd, float* __restrict__ pit,
@@ -243,28 +266,39 @@ __global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc
     for (int32_t m = 0; m < M; ++m) {
       const float a0 = aux[m * 3], a1 = aux[m * 3 + 1], a2 = aux[m * 3 + 2];
       const float l = loc[(int64_t)m * R + r];
+      double w = 1.0;
+      if constexpr (WEIGHTED) w = wts[m];
       if (lpd) {
         const float lp = score_log_density<OBS>(yv, l, a0, a1, a2);
         const float nm = fmaxf(mx, lp);
         if (nm > -INFINITY) {
-          s = s * (double)expf(mx - nm) + (double)expf(lp - nm);
+          if constexpr (WEIGHTED) s = s * (double)expf(mx - nm) + w * (double)expf(lp - nm);
+          else s = s * (double)expf(mx - nm) + (double)expf(lp - nm);
           mx = nm;
         }
       }
       if constexpr (OBS == BNF_OBS_NORMAL) {
         if (normal_sums) {
           const float d = yv - l;
-          cdf += (double)ndtrf(d / a0);
-          first += (double)score_abs_moment(d, 0.70710678118654752440f / a0, a0 * 0.79788456080286535588f);
-          diag += (double)a0;
+          const float cm = ndtrf(d / a0);
+          const float am = score_abs_moment(d, 0.70710678118654752440f / a0, a0 * 0.79788456080286535588f);
+          if constexpr (WEIGHTED) {
+            cdf += w * (double)cm;
+            first += w * (double)am;
+            diag += (w * w) * (double)a0;
+          } else {
+            cdf += (double)cm;
+            first += (double)am;
+            diag += (double)a0;
+          }
         }
       }
     }
   }
-  if (lpd) lpd[r] = mx + logf((float)(s / (double)M));
+  if (lpd) lpd[r] = mx + logf((float)(WEIGHTED ? s : s / (double)M));
   if constexpr (OBS == BNF_OBS_NORMAL) {
     if (pit) {
-      const float f = (float)(cdf / (double)M);
+      const float f = (float)(WEIGHTED ? cdf : cdf / (double)M);
       pit[r] = f;
       pit[R + r] = f;
     }
@@ -274,7 +308,8 @@ __global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc
       double pairs = 0.0;
       for (int32_t p = 0; p < n_partial; ++p) pairs += pair_partial[(int64_t)p * R + r];
       const double dm = (double)M;
-      crps[r] = (float)(first / dm - (pairs + diag * 0.56418958354775628695) / (dm * dm));
+      if constexpr (WEIGHTED) crps[r] = (float)(first - (pairs + diag * 0.56418958354775628695));
+      else crps[r] = (float)(first / dm - (pairs + diag * 0.56418958354775628695) / (dm * dm));
     }
   }
 }
@@ -282,8 +317,9 @@ __global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc
 // pit of the count models: count_mix_cdf (bnf_kernels.h, f64 for the reason given there) at floor(y) (blockIdx.y = 0) and
 // at the largest integer below y (blockIdx.y = 1), 0 below the support.  One lane per (row, side).  `flatten`: left to
 // itself hipcc calls count_mix_cdf as a function, and the call stack is 268 bytes of scratch per lane; inlined there is none.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(64) __attribute__((flatten)) void k_score_count_pit(const float* __restrict__ loc, const float* __restrict__ aux,
-                                                        int32_t M, int64_t R, int32_t obs, const float* __restrict__ y,
+                                                        const double* __restrict__ wts, int32_t M, int64_t R, int32_t obs, const float* __restrict__ y,
                                                         float* __restrict__ pit) {
   const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (r >= R) return;
@@ -292,7 +328,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_score_count_pit
   if (!score_finite(yv)) { out[r] = __builtin_nanf(""); return; }
   const float yf = floorf(yv);
   const float x = blockIdx.y == 0 ? yf : (yv == yf ? yf - 1.0f : yf);
-  out[r] = x < 0.f ? 0.f : count_mix_cdf(loc, aux, M, R, obs, r, x);
+  out[r] = x < 0.f ? 0.f : count_mix_cdf<WEIGHTED>(loc, aux, wts, M, R, obs, r, x);
 }
 
 }  // namespace bnf

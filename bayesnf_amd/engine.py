@@ -242,30 +242,69 @@ class Engine:
                                        _ptr(loc), _ptr(aux)), 'bnf_forward')
     return loc, aux
 
+  def _kept(self, weights, per_member, per_row):
+    """Member weights (M,) for the *_weighted entry points -> (w, per_member, per_row) on the device without the members
+    of weight exactly 0 (a device index_select along dim 0): such a member plays no part at all -- it neither widens a
+    quantile bracket or an RPS window nor hands on a NaN.  The weights are taken as they come (`inference.mixture_weights`
+    validates them); weights that are all zero are a ValueError."""
+    M = per_row.shape[0]
+    w = self._as_f64(weights, (M,), 'weights')
+    keep = torch.nonzero(w != 0).flatten()
+    if keep.numel() == 0:
+      raise ValueError('weights: every member has weight 0')
+    if keep.numel() == M:
+      return w, per_member, per_row
+    return (w.index_select(0, keep).contiguous(), per_member.index_select(0, keep).contiguous(),
+            per_row.index_select(0, keep).contiguous())
+
   def normal_mixture_quantiles(self, means: torch.Tensor, scales: torch.Tensor,
-                               quantiles, approximate=False) -> torch.Tensor:
-    """means (M, R), scales (M,) -> (n_q, R)."""
+                               quantiles, approximate=False, weights=None) -> torch.Tensor:
+    """means (M, R), scales (M,) -> (n_q, R).  weights (M,) array or device tensor: the quantiles of the mixture
+    sum_m w_m N(mu_m, s_m) (bnf_normal_mixture_quantiles_weighted) after the members of weight 0 are dropped; None: the
+    equal-weight call, bit for bit."""
     means = means.contiguous().float()
     scales = scales.contiguous().float()
     q = np.asarray(list(quantiles), dtype=np.float32)
     out = torch.empty((len(q), means.shape[1]), dtype=torch.float32, device=self.device)
     qa = (C.c_float * len(q))(*q.tolist())
-    _native.check(self.lib.bnf_normal_mixture_quantiles(
-        self.handle, _ptr(means), _ptr(scales), means.shape[0], means.shape[1], qa,
-        len(q), 1 if approximate else 0, _ptr(out)), 'bnf_normal_mixture_quantiles')
+    if weights is None:
+      _native.check(self.lib.bnf_normal_mixture_quantiles(
+          self.handle, _ptr(means), _ptr(scales), means.shape[0], means.shape[1], qa,
+          len(q), 1 if approximate else 0, _ptr(out)), 'bnf_normal_mixture_quantiles')
+      return out
+    w, scales, means = self._kept(weights, scales, means)
+    _native.check(self.lib.bnf_normal_mixture_quantiles_weighted(
+        self.handle, _ptr(means), _ptr(scales), _ptr(w), means.shape[0], means.shape[1], qa,
+        len(q), 1 if approximate else 0, _ptr(out)), 'bnf_normal_mixture_quantiles_weighted')
+    torch.cuda.synchronize(self.device)     # `w` and the kept members' copies are released on return
     return out
 
-  def count_mixture_quantiles(self, loc: torch.Tensor, aux: torch.Tensor, quantiles):
-    """NB / ZINB: loc (M, R) network output, aux (M, 3) -> (means (M, R), quantiles (n_q, R))."""
+  def count_mixture_quantiles(self, loc: torch.Tensor, aux: torch.Tensor, quantiles, weights=None):
+    """NB / ZINB: loc (M, R) network output, aux (M, 3) -> (means (M, R), quantiles (n_q, R)).  weights (M,) array or
+    device tensor: the quantiles of the weighted mixture (bnf_count_mixture_quantiles_weighted) after the members of
+    weight 0 are dropped; the per-member means are those of every member either way.  None: the equal-weight call."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     q = np.asarray(list(quantiles), dtype=np.float32)
     means = torch.empty_like(loc)
     out = torch.empty((len(q), loc.shape[1]), dtype=torch.float32, device=self.device)
     qa = (C.c_float * max(1, len(q)))(*q.tolist())
-    _native.check(self.lib.bnf_count_mixture_quantiles(
-        self.handle, _ptr(loc), _ptr(aux), loc.shape[0], loc.shape[1], qa, len(q),
-        _ptr(means), _ptr(out)), 'bnf_count_mixture_quantiles')
+    if weights is None:
+      _native.check(self.lib.bnf_count_mixture_quantiles(
+          self.handle, _ptr(loc), _ptr(aux), loc.shape[0], loc.shape[1], qa, len(q),
+          _ptr(means), _ptr(out)), 'bnf_count_mixture_quantiles')
+      return means, out
+    w, kaux, kloc = self._kept(weights, aux, loc)
+    kmeans = means
+    if kloc.shape[0] != loc.shape[0]:       # the means of all members: the unweighted call without levels
+      _native.check(self.lib.bnf_count_mixture_quantiles(
+          self.handle, _ptr(loc), _ptr(aux), loc.shape[0], loc.shape[1], qa, 0, _ptr(means), None),
+          'bnf_count_mixture_quantiles')
+      kmeans = torch.empty_like(kloc)
+    _native.check(self.lib.bnf_count_mixture_quantiles_weighted(
+        self.handle, _ptr(kloc), _ptr(kaux), _ptr(w), kloc.shape[0], kloc.shape[1], qa, len(q),
+        _ptr(kmeans), _ptr(out)), 'bnf_count_mixture_quantiles_weighted')
+    torch.cuda.synchronize(self.device)     # `w` and the kept members' copies are released on return
     return means, out
 
   def _cum(self, cum_weights, M):
@@ -334,14 +373,17 @@ class Engine:
     return out
 
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
-                        lpd=True, pit=True) -> dict:
+                        lpd=True, pit=True, weights=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),
     aux (M, 3) as `forward` returns them -> dict of device tensors, one per output asked for:
       'member_ll' (M,) f64   sum over the rows with a finite y of each member's log density
       'lpd' (R,) f32         log density of the equal-weight mixture
       'pit' (2, R) f32       mixture CDF at y and just below y
       'crps' (R,) f32        NORMAL only (crps=None: exactly then; crps=True on a count handle is the library's error)
-    Rows whose y is NaN come back NaN and do not enter member_ll.  Deterministic: the same call gives the same bits."""
+    Rows whose y is NaN come back NaN and do not enter member_ll.  Deterministic: the same call gives the same bits.
+    weights (M,) array or device tensor: 'lpd', 'pit' and 'crps' are those of the mixture sum_m w_m p_m
+    (bnf_predictive_scores_weighted) after the members of weight 0 are dropped; 'member_ll' is per member and comes from
+    the unweighted call on all members.  None: the equal-weight call, bit for bit."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
@@ -351,6 +393,24 @@ class Engine:
       raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
     if crps is None:
       crps = self.net.observation_model == 'NORMAL'
+    if weights is not None:
+      out = self.predictive_scores(loc, aux, y, crps=False, member_ll=True, lpd=False, pit=False) if member_ll else {}
+      w, aux, loc = self._kept(weights, aux, loc)
+      M = loc.shape[0]
+      if lpd:
+        out['lpd'] = torch.empty((R,), dtype=torch.float32, device=self.device)
+      if pit:
+        out['pit'] = torch.empty((2, R), dtype=torch.float32, device=self.device)
+      if crps:
+        out['crps'] = torch.empty((R,), dtype=torch.float32, device=self.device)
+      n_chunks = -(-M // _native.SCORE_MEMBER_CHUNK)
+      n_work = R * min((n_chunks + 1) // 2, _native.SCORE_MAX_SLOTS) if crps else 0
+      work = torch.empty(max(1, n_work), dtype=torch.float64, device=self.device)
+      _native.check(self.lib.bnf_predictive_scores_weighted(
+          self.handle, _ptr(loc), _ptr(aux), _ptr(w), M, R, _ptr(y), _ptr(work), C.c_size_t(n_work * 8),
+          _ptr(out.get('lpd')), _ptr(out.get('pit')), _ptr(out.get('crps'))), 'bnf_predictive_scores_weighted')
+      torch.cuda.synchronize(self.device)   # `work`, `w` and the kept members' copies are released on return
+      return out
     out = {}
     if member_ll:
       out['member_ll'] = torch.empty((M,), dtype=torch.float64, device=self.device)
@@ -371,11 +431,13 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work` and the device copy of `y` are released on return
     return out
 
-  def count_rps(self, loc: torch.Tensor, aux: torch.Tensor, y) -> torch.Tensor:
+  def count_rps(self, loc: torch.Tensor, aux: torch.Tensor, y, weights=None) -> torch.Tensor:
     """NB / ZINB: the ranked probability score -- the CRPS of a count forecast -- of the observations y (R,) against
     the equal-weight mixture over members (include/bnf.h bnf_count_rps): loc (M, R), aux (M, 3) as `forward` returns
     them -> (R,) f32 on the device.  NaN where y is NaN, negative or not an integer, and where the row's window is longer
-    than BNF_RPS_MAX_TERMS.  A NORMAL handle is the library's error (ValueError).  Deterministic."""
+    than BNF_RPS_MAX_TERMS.  A NORMAL handle is the library's error (ValueError).  Deterministic.
+    weights (M,) array or device tensor: the score of the weighted mixture (bnf_count_rps_weighted) after the members
+    of weight 0 are dropped -- such a member cannot cap a row; None: the equal-weight call, bit for bit."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
@@ -384,6 +446,12 @@ class Engine:
     if y.shape != (R,):
       raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
     out = torch.empty((R,), dtype=torch.float32, device=self.device)
+    if weights is not None:
+      w, aux, loc = self._kept(weights, aux, loc)
+      _native.check(self.lib.bnf_count_rps_weighted(self.handle, _ptr(loc), _ptr(aux), _ptr(w), loc.shape[0], R, _ptr(y),
+                                                    _ptr(out)), 'bnf_count_rps_weighted')
+      torch.cuda.synchronize(self.device)   # `w`, the kept members' copies and the device copy of `y` are released
+      return out
     _native.check(self.lib.bnf_count_rps(self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(out)), 'bnf_count_rps')
     torch.cuda.synchronize(self.device)     # the device copy of `y` is released on return
     return out

@@ -281,10 +281,14 @@ def _ensemble_forecast(features, observation_model, params, model_args,
 
 
 def predict_bnf(features, observation_model, params, model_args, quantiles,
-                ensemble_dims=2, approximate_quantiles=False, compute_dtype=None):
+                ensemble_dims=2, approximate_quantiles=False, compute_dtype=None, weights=None):
   """-> (means, [quantile arrays]).  means: leading ensemble dims of `params`
-  + (n_rows,); each quantile array has shape (n_rows,)."""
+  + (n_rows,); each quantile array has shape (n_rows,).
+  weights (shape of the ensemble dims, `mixture_weights`): the quantiles are those of the weighted mixture over the
+  members -- the weights `stack_members` returns; the per-member means do not change.  None: equal weights."""
   assert ensemble_dims >= 1
+  w, _ = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if w is None else {'weights': w}
   features = np.asarray(features, dtype=np.float64)
   net, eng, lead, loc_all, aux_all = _ensemble_forecast(
       features, observation_model, params, model_args, ensemble_dims, compute_dtype)
@@ -293,10 +297,10 @@ def predict_bnf(features, observation_model, params, model_args, quantiles,
   if observation_model == 'NORMAL':
     means = loc
     q = eng.normal_mixture_quantiles(means, aux_all.reshape(-1, 3)[:, 0], quantiles,
-                                     approximate=approximate_quantiles)
+                                     approximate=approximate_quantiles, **kw)
   else:
     # NB / ZINB (inference.py:493-502): distribution means + root-found integer quantiles
-    means, q = eng.count_mixture_quantiles(loc, aux_all.reshape(-1, 3), quantiles)
+    means, q = eng.count_mixture_quantiles(loc, aux_all.reshape(-1, 3), quantiles, **kw)
   torch.cuda.synchronize(eng.device)
   means_np = means.cpu().numpy().reshape(tuple(lead) + (n_rows,))
   q_np = q.cpu().numpy()
@@ -456,10 +460,12 @@ def total_summaries(features, observation_model, params, model_args, num_samples
 # scores of held-out observations
 # ---------------------------------------------------------------------------
 def score_predictive(features, target, observation_model, params, model_args, ensemble_dims, compute_dtype=None,
-                     rps=False):
+                     rps=False, weights=None):
   """Held-out observations `target` (n_rows,) scored against the ensemble on the GPU (include/bnf.h
-  bnf_predictive_scores).  Every leading ensemble dim of `params` flattens to the M equally weighted mixture
-  components, exactly as in predict_bnf.  NaN targets are allowed: their rows come back NaN and do not enter the
+  bnf_predictive_scores).  Every leading ensemble dim of `params` flattens to the M mixture components, exactly as in
+  predict_bnf: equally weighted, or with `weights` (shape of the ensemble dims, `mixture_weights`; the weights
+  `stack_members` returns) -- then 'log_density', 'pit', 'crps' and 'rps' are those of the weighted mixture
+  (bnf_predictive_scores_weighted, bnf_count_rps_weighted) and 'member_log_prob' does not change.  NaN targets are allowed: their rows come back NaN and do not enter the
   per-member sums.  -> dict of numpy arrays:
     'log_density' (n_rows,) float32      log density of the mixture at the target
     'pit' (2, n_rows) float32            mixture CDF at the target and just below it (equal for NORMAL)
@@ -476,17 +482,19 @@ def score_predictive(features, target, observation_model, params, model_args, en
   n_rows = features.shape[0]
   if target.shape != (n_rows,):
     raise ValueError(f'target must hold one observation per row ({n_rows},); got {target.shape}')
+  w, _ = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if w is None else {'weights': w}
   net, eng, lead, loc_all, aux_all = _ensemble_forecast(
       features, observation_model, params, model_args, ensemble_dims, compute_dtype)
   try:
     loc, aux, y32 = loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), np.ascontiguousarray(target, dtype=np.float32)
-    res = eng.predictive_scores(loc, aux, y32)
+    res = eng.predictive_scores(loc, aux, y32, **kw)
     out = {'log_density': res['lpd'].cpu().numpy(), 'pit': res['pit'].cpu().numpy(),
            'member_log_prob': res['member_ll'].cpu().numpy().reshape(tuple(lead))}
     if 'crps' in res:
       out['crps'] = res['crps'].cpu().numpy()
     if rps:
-      out['rps'] = eng.count_rps(loc, aux, y32).cpu().numpy()
+      out['rps'] = eng.count_rps(loc, aux, y32, **kw).cpu().numpy()
     return out
   finally:
     eng.close()
@@ -504,8 +512,8 @@ def stack_members(features, target, observation_model, params, model_args, ensem
     'objective', 'objective_start'   mean log density over the scored rows at the returned / the starting weights
     'gap', 'iterations', 'converged', 'dropped'   dropped: rows to which every member with a positive weight gives the
                                                   density 0 (left out of the means)
-  Only the sample-path family takes the weights (`sample_predictive`, `total_summaries`): the marginal quantiles of
-  predict_bnf and the pit / crps / rps of score_predictive stay those of the equal-weight mixture, and fit is untouched."""
+  The weights are taken by the sample-path family (`sample_predictive`, `total_summaries`) and by the marginal forecast:
+  the quantiles of predict_bnf and the log density / pit / crps / rps of score_predictive; fit is untouched."""
   w0, _ = mixture_weights(weights, params, ensemble_dims)
   max_iter = int(max_iter)
   tol = float(tol)
@@ -534,13 +542,29 @@ def _quantile_engine(net, obs, compute_dtype):
   return Engine(net, mode='map', members=1, forward_only=True, row_capacity=128, compute_dtype=compute_dtype)
 
 
+def _lead_weights(weights, lead):
+  """Member weights of a likelihood object, shape of its ensemble dims `lead` -> (M,) float64 in member order."""
+  w = np.asarray(weights, dtype=np.float64)
+  if w.shape != tuple(lead):
+    raise ValueError(f'weights must have the shape of the ensemble dims {tuple(lead)}; got {w.shape}')
+  return np.ascontiguousarray(w.reshape(-1))
+
+
+def _mixture_cdf(c, weights):
+  """Per-member cdf c (*ens, R) -> the mixture's (R,): the mean over members, or the sum weighted by `weights` (*ens)."""
+  if weights is None:
+    return c.reshape(-1, c.shape[-1]).mean(axis=0)
+  return _lead_weights(weights, c.shape[:-1]) @ c.reshape(-1, c.shape[-1])
+
+
 class EnsembleLikelihood:
   """Stand-in for the TFP distribution returned by the reference's `likelihood_model`
   (spatiotemporal.py:433-468): Independent Normal per member with event shape (n_rows,) and
   batch shape = ensemble dims.  mean / stddev / log_prob / sample are per member (as TFP's);
   cdf is the per-member, per-row Normal cdf; mixture_cdf / quantile treat the ensemble as the
   equally weighted mixture `predict` reports quantiles of (inference.py:42-52), the root found
-  on the GPU by the same kernel (`bnf_normal_mixture_quantiles`)."""
+  on the GPU by the same kernel (`bnf_normal_mixture_quantiles`); with weights= (shape of the ensemble
+  dims, on the simplex) as the weighted mixture (`bnf_normal_mixture_quantiles_weighted`)."""
 
   def __init__(self, loc: np.ndarray, scale: np.ndarray, net=None, compute_dtype=None):
     self.loc = loc                       # (*ens, R)
@@ -562,17 +586,17 @@ class EnsembleLikelihood:
     from scipy import special as sp
     return sp.ndtr((np.asarray(x, dtype=np.float64) - self.loc) / self.scale)
 
-  def mixture_cdf(self, x):
-    c = self.cdf(x)
-    return c.reshape(-1, c.shape[-1]).mean(axis=0)
+  def mixture_cdf(self, x, weights=None):
+    return _mixture_cdf(self.cdf(x), weights)
 
-  def quantile(self, q, approximate=False):
+  def quantile(self, q, approximate=False, weights=None):
     """Mixture quantile(s) per row: q scalar -> (R,), sequence -> (len(q), R)."""
+    kw = {} if weights is None else {'weights': _lead_weights(weights, self.loc.shape[:-1])}
     qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
     eng = _quantile_engine(self._net, 'NORMAL', self._dtype)
     means = torch.from_numpy(np.ascontiguousarray(self.loc.reshape(-1, self.loc.shape[-1]), dtype=np.float32)).to(eng.device)
     scales = torch.from_numpy(np.ascontiguousarray(self.scale.reshape(-1), dtype=np.float32)).to(eng.device)
-    out = eng.normal_mixture_quantiles(means, scales, qs.tolist(), approximate=approximate)
+    out = eng.normal_mixture_quantiles(means, scales, qs.tolist(), approximate=approximate, **kw)
     torch.cuda.synchronize(eng.device)
     res = out.cpu().numpy().astype(np.float64)
     eng.close()
@@ -634,16 +658,16 @@ class CountEnsembleLikelihood:
       c = np.where(x < 0, 0.0, self.inflated_loc_probs + (1.0 - self.inflated_loc_probs) * c)
     return c
 
-  def mixture_cdf(self, x):
-    c = self.cdf(x)
-    return c.reshape(-1, c.shape[-1]).mean(axis=0)
+  def mixture_cdf(self, x, weights=None):
+    return _mixture_cdf(self.cdf(x), weights)
 
-  def quantile(self, q):
+  def quantile(self, q, weights=None):
+    kw = {} if weights is None else {'weights': _lead_weights(weights, self._loc.shape[:-1])}
     qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
     eng = Engine(self._net, mode='map', members=1, forward_only=True, row_capacity=128, compute_dtype=self._dtype)
     loc = torch.from_numpy(np.ascontiguousarray(self._loc.reshape(-1, self._loc.shape[-1]), dtype=np.float32)).to(eng.device)
     aux = torch.from_numpy(np.ascontiguousarray(self._aux.reshape(-1, 3), dtype=np.float32)).to(eng.device)
-    _, out = eng.count_mixture_quantiles(loc, aux, qs.tolist())
+    _, out = eng.count_mixture_quantiles(loc, aux, qs.tolist(), **kw)
     torch.cuda.synchronize(eng.device)
     res = out.cpu().numpy().astype(np.float64)
     eng.close()

@@ -346,13 +346,16 @@ class BayesianNeuralFieldEstimator:
   def fit(self, table, seed):
     raise NotImplementedError('Should be implemented by subclass')
 
-  def predict(self, table, quantiles=(0.5,), approximate_quantiles=False):
+  def predict(self, table, quantiles=(0.5,), approximate_quantiles=False, weights=None):
     """-> (means, quantiles): means has shape
     (num_devices, ensemble_size // num_devices, len(table)) (VI: an extra
     posterior-sample axis after num_devices); quantiles is a list with one
     (len(table),) array per requested level, for the equal-weight mixture of
     all members.  Exact quantiles use Chandrupatla root finding; approximate
-    ones the moment-matched Normal."""
+    ones the moment-matched Normal.
+    weights (the shape of `score(...)['member_log_prob']`, e.g. `stacking_weights(...)['weights']`): the quantiles are
+    those of the weighted mixture of members; `means` is per member and does not change.  None: equal weights."""
+    kw = self._weights_kw(weights)
     rows = self.data_handler.get_test(table)
     return inference.predict_bnf(
         rows,
@@ -363,6 +366,7 @@ class BayesianNeuralFieldEstimator:
         ensemble_dims=self._ensemble_dims,
         approximate_quantiles=approximate_quantiles,
         compute_dtype=self.compute_dtype,
+        **kw,
     )
 
   def predict_samples(self, table, num_samples=1000, seed=0, group_by=None, weights=None):
@@ -432,8 +436,8 @@ class BayesianNeuralFieldEstimator:
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals` and `score_totals` (weights=...) and scored on
-    another table by `weighted_log_density`.  Out of scope: `predict`'s marginal quantiles and `score`'s pit / crps /
-    rps stay those of the equal-weight mixture, and `fit` is unchanged."""
+    another table by `weighted_log_density`; they are taken by the marginal forecast as well: `predict` and `score`
+    (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.  `fit` is unchanged."""
     if self.params_ is None:
       raise ValueError('stacking_weights before fit')
     res = self._stack('stacking_weights', table, None, max_iter, tol)
@@ -457,7 +461,7 @@ class BayesianNeuralFieldEstimator:
     lpd = res['log_density']
     return {'log_density': lpd, 'mean_log_density': res['objective'], 'n': int(np.isfinite(lpd).sum())}
 
-  def score(self, table, rps=False):
+  def score(self, table, rps=False, weights=None):
     """The forecast at the rows of `table` scored against the observations `table[target_col]`, on the GPU.  NaN
     targets are allowed: their rows are reported as NaN and left out of every sum and mean.  rps=True (NB / ZINB;
     ValueError on NORMAL, whose score of this kind is 'crps') adds the ranked probability score, the CRPS of a count
@@ -474,7 +478,10 @@ class BayesianNeuralFieldEstimator:
                           that the sum would take more than 2^20 terms (a mean of 1e6 at total_count 0.05 is)
       'mean_rps'          rps=True: mean over the scored rows whose 'rps' is not NaN
       'rps_capped'        rps=True: the rows with a finite target whose 'rps' is NaN -- capped, or a member whose
-                          parameters are not finite (0 at any realistic count forecast)"""
+                          parameters are not finite (0 at any realistic count forecast)
+    weights (the shape of 'member_log_prob', e.g. `stacking_weights(...)['weights']`): 'log_density', 'pit', 'crps',
+    'rps' and their 'mean_*' / 'rps_capped' are those of the weighted mixture of members -- the forecast whose
+    quantiles `predict(weights=...)` reports; 'member_log_prob' and 'n' do not change.  None: equal weights."""
     if self.params_ is None:
       raise ValueError('score before fit')
     if rps and self.observation_model == 'NORMAL':
@@ -487,10 +494,11 @@ class BayesianNeuralFieldEstimator:
     seen = y[np.isfinite(y)]
     if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
       raise ValueError(f'score: the {self.observation_model} observation model takes non-negative integer targets')
+    kw = self._weights_kw(weights)
     rows = self.data_handler.get_test(table)
     out = inference.score_predictive(
         rows, y, self.observation_model, self.params_, self._model_args(rows.shape),
-        ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype, rps=bool(rps))
+        ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype, rps=bool(rps), **kw)
     out['n'] = int(seen.size)
     for key in ('log_density', 'crps'):
       if key in out:

@@ -368,6 +368,39 @@ int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int
 int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
                   const float* y, float* rps);
 
+/* The MARGINAL FORECAST OF THE WEIGHTED MIXTURE sum_m w_m p_m: the four calls above with member weights (the weights
+ * bnf_stacking_weights finds), each with the arguments of its sibling plus
+ *   weights DEVICE (n_members,) f64, w_m >= 0, sum_m w_m = 1 -- the layout bnf_stacking_weights writes, so learned weights
+ *     pass through without a host trip.  NULL is BNF_ERR_INVALID: the unweighted call has its own name.
+ * bnf_normal_mixture_quantiles_weighted: approximate=0 the Chandrupatla root of sum_m w_m Phi((x - mu_m) / sigma_m) - q
+ *   (bracket, tolerances and iteration cap of the unweighted call); approximate=1 the moment-matched Normal with
+ *   mean = sum w mu, var = sum w (sigma^2 + mu^2) - mean^2.
+ * bnf_count_mixture_quantiles_weighted: ceil of the root of sum_m w_m cdf_m(x) - q, 0 where sum_m w_m pmf_m(0) > q; the
+ *   per-member `means` are unchanged.
+ * bnf_predictive_scores_weighted: lpd = log sum_m w_m p_m(y_r) (log space, running max), pit = the weighted mixture CDF at
+ *   y_r and just below it, crps (NORMAL only) = sum_i w_i A(y - mu_i, s_i) - [sum_{j<i} w_i w_j A(mu_i - mu_j,
+ *   sqrt(s_i^2 + s_j^2)) + sum_i w_i^2 s_i / sqrt(pi)].  No member_ll: it is per member, weights do not touch it.  work:
+ *   the crps part of bnf_predictive_scores' formula only.
+ * bnf_count_rps_weighted: F_r = sum_m w_m F_{m,r}, P0 = sum_m w_m pi_m; window, eps, cap and BNF_RPS_MAX_MEMBERS as for
+ *   bnf_count_rps (a weighted mean of tails that are each below eps is below eps: bnf_rps.h).
+ * Every sum over members is f64 -- w_m times the f32 term converted to double -- in an order the shapes fix, no
+ * floating-point atomics: two calls give the same bits.  The weights are NOT validated (the library cannot read them
+ * without a sync): weights off the simplex give meaningless numbers, never an access outside loc / aux / weights.  A
+ * member of weight exactly 0 adds nothing to any sum but still widens the quantile bracket and the RPS window (it can cap
+ * a row), and a NaN in its parameters still propagates: drop such members before the call (the Python wrappers do).
+ * Run on the handle's stream, do not touch the training state, work on forward-only handles. */
+int bnf_normal_mixture_quantiles_weighted(bnf_handle* h, const float* means, const float* scales, const double* weights,
+                                          int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
+                                          int32_t approximate, float* out);
+int bnf_count_mixture_quantiles_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
+                                         int64_t n_members, int64_t n_rows, const float* q, int32_t n_q, float* means,
+                                         float* out);
+int bnf_predictive_scores_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
+                                   int64_t n_members, int64_t n_rows, const float* y, void* work, size_t work_bytes,
+                                   float* lpd, float* pit, float* crps);
+int bnf_count_rps_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights, int64_t n_members,
+                           int64_t n_rows, const float* y, float* rps);
+
 /* The matrix of per-member LOG DENSITIES of held-out observations: out DEVICE (n_members, n_rows) f32,
  * out[m][r] = log p_m(y_r), the f32 terms whose sums over r bnf_predictive_scores reports as member_ll (the forms of the
  * training loss, bnf_scoring.h).  loc, aux, y as for bnf_predictive_scores.  Every member of a row whose y is NaN or
