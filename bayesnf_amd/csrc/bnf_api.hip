@@ -33,6 +33,7 @@
 #include "bnf_panel.h"
 #include "bnf_gemm8.h"
 #include "bnf_sampling.h"
+#include "bnf_extremes.h"
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
@@ -1393,6 +1394,21 @@ static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const 
                      seg_offsets, (int32_t)G, R, S, partial, out);
 }
 
+// group peaks and exceedances of the same paths (bnf_extremes.h): the launch shape of the group sums
+template <int OBS>
+static void launch_predictive_group_extremes(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
+                                             const int32_t* seg_offsets, int64_t G, int64_t S, uint64_t seed, int64_t row0,
+                                             int64_t sample0, const double* cum, const float* threshold, ExtPiece* partial,
+                                             const ExtOut& o, uint32_t* exceed_count) {
+  const int64_t nt = cdiv(R, kPredTile);
+  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
+  hipLaunchKernelGGL((k_predictive_group_extremes<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc,
+                     aux, (int32_t)M, R, seg_offsets, o.seg_rows, (int32_t)G, S, seed, row0, sample0, cum, threshold,
+                     partial, o, exceed_count);
+  hipLaunchKernelGGL(k_predictive_group_extremes_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
+                     seg_offsets, (int32_t)G, R, S, partial, o);
+}
+
 // held-out scoring launches (bnf_scoring.h), one instantiation per observation model and for the member weights wts
 // (WEIGHTED: wts non-null, no member_ll)
 template <int OBS, bool WEIGHTED>
@@ -2110,6 +2126,43 @@ int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const fl
   if (const int rc = no_device()) return rc;
   return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
                                     sample0, cum_weights, work, work_bytes, out);
+}
+
+// ---- group peaks and threshold exceedances of the sample paths (bnf_extremes.h) ----
+int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
+                                  const float* threshold, void* work, size_t work_bytes, double* out_max,
+                                  int32_t* out_argmax, double* out_count, uint32_t* peak_count, uint32_t* exceed_count) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || !work || !out_max || n_groups < 1 || n_groups > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if ((threshold == nullptr) != (out_count == nullptr) || (exceed_count && !threshold))
+    return fail(BNF_ERR_INVALID, "out_count goes with threshold, and exceed_count needs one");
+  const int64_t nt = cdiv(n_rows, kPredTile);
+  const size_t per_sample = (size_t)nt * BNF_EXTREMES_WORK_PER_TILE;
+  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
+  if (chunk < 1)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
+                (long long)n_rows, per_sample);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // groups without a row: max NaN (all bits set), argmax -1, count 0
+  const size_t cells = (size_t)n_samples * (size_t)n_groups;
+  HIPCHK(hipMemsetAsync(out_max, 0xff, cells * sizeof(double), h->stream));
+  if (out_argmax) HIPCHK(hipMemsetAsync(out_argmax, 0xff, cells * sizeof(int32_t), h->stream));
+  if (out_count) HIPCHK(hipMemsetAsync(out_count, 0, cells * sizeof(double), h->stream));
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
+    const int64_t n = std::min(chunk, n_samples - s0);
+    const ExtOut o{seg_rows, out_max + s0 * n_groups, out_argmax ? out_argmax + s0 * n_groups : nullptr,
+                   out_count ? out_count + s0 * n_groups : nullptr, peak_count};
+    switch (h->cfg.obs_model) {
+      case BNF_OBS_NORMAL: launch_predictive_group_extremes<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
+      case BNF_OBS_NB: launch_predictive_group_extremes<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
+      default: launch_predictive_group_extremes<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
 }
 
 // ---- held-out scoring (bnf_scoring.h) ---------------------------------------------

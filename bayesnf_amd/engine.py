@@ -372,6 +372,54 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
     return out
 
+  def predictive_group_extremes(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
+                                threshold=None, row0=0, sample0=0, cum_weights=None, per_row=True) -> dict:
+    """Peaks and threshold exceedances of the same sample paths over groups of rows (include/bnf.h
+    bnf_predictive_group_extremes), without materialising the draws; loc, aux, seg_offsets, seg_rows, row0, sample0 and
+    cum_weights as for `predictive_group_sums`.  -> dict of device tensors:
+      'max' (n_samples, G) f64       the largest draw over the group's rows (a NaN draw counts as -inf)
+      'argmax' (n_samples, G) int32  the table row at which it is first reached: ties go to the lowest position of seg_rows
+      'count' (n_samples, G) f64     with `threshold` (R,) f32, one limit per table row: the rows whose draw is > their limit
+      'peak_count' (R,) int32        per_row=True: the paths in which the row is its group's argmax
+      'exceed_count' (R,) int32      per_row=True with `threshold`: the paths whose draw at the row is > its limit
+    A group without rows gives max NaN, argmax -1, count 0.  Deterministic: the same call gives the same bits."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+                        ).to(self.device, dtype=torch.int32).contiguous()
+    off, rows = as_i32(seg_offsets), as_i32(seg_rows)
+    G = off.numel() - 1
+    if G < 1 or rows.numel() != R:
+      raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
+    thr = None
+    if threshold is not None:
+      thr = (threshold if isinstance(threshold, torch.Tensor)
+             else torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32))).to(self.device, dtype=torch.float32).contiguous()
+      if tuple(thr.shape) != (R,):
+        raise ValueError(f'threshold must hold one limit per row ({R},); got {tuple(thr.shape)}')
+    n_samples = int(n_samples)
+    out = {'max': torch.empty((n_samples, G), dtype=torch.float64, device=self.device),
+           'argmax': torch.empty((n_samples, G), dtype=torch.int32, device=self.device)}
+    if thr is not None:
+      out['count'] = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+    if per_row:                             # the library adds to these: zeroed here
+      out['peak_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+      if thr is not None:
+        out['exceed_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+    # per-tile pieces: BNF_EXTREMES_WORK_PER_TILE bytes per tile and path, at most ~64 MB (the library makes several
+    # passes beyond that)
+    per_path = _native.EXTREMES_WORK_PER_TILE * (-(-R // _native.GROUP_TILE))
+    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // per_path)), dtype=torch.uint8, device=self.device)
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_group_extremes(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(thr), _ptr(work),
+        C.c_size_t(work.numel()), _ptr(out['max']), _ptr(out['argmax']), _ptr(out.get('count')),
+        _ptr(out.get('peak_count')), _ptr(out.get('exceed_count'))), 'bnf_predictive_group_extremes')
+    torch.cuda.synchronize(self.device)     # `work`, `off`, `rows`, `thr` and `cum` are released on return
+    return out
+
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
                         lpd=True, pit=True, weights=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),

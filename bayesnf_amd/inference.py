@@ -456,6 +456,78 @@ def total_summaries(features, observation_model, params, model_args, num_samples
     eng.close()
 
 
+def extreme_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                      threshold=None, observed_max=None, observed_count=None, quantiles=(), compute_dtype=None,
+                      weights=None):
+  """Group peaks and threshold exceedances of the joint sample paths, summarised and scored on the GPU: per path and
+  group the largest draw, the row where it is first reached and the number of rows above their threshold are formed
+  without materialising the draws (include/bnf.h bnf_predictive_group_extremes); the (num_samples, G) matrices stay on the
+  device and go through bnf_sample_summaries.  groups = (seg_offsets, seg_rows) as `csr_from_codes` builds them;
+  threshold (n_rows,) finite, in the units of the draws, compared with strict >; observed_max / observed_count (G,) the
+  observed peak value / number of exceedances, NaN where a group is not to be scored.  -> dict of numpy arrays:
+    'max_mean' (G,)  'max_quantiles' (len(quantiles), G)   of the group's peak value, numpy's default 'linear' rule
+    'max_crps' (G,)  'max_pit' (2, G)                      with observed_max, as `total_summaries` forms them
+    'peak_probability' (n_rows,)                           share of the paths in which the row is where its group first
+                                                           reaches its maximum (ties: the lowest table row)
+  and with `threshold`:
+    'count_mean', 'count_quantiles', ('count_crps', 'count_pit' with observed_count)   of the number of rows above
+    'exceed_any' (G,)                                      share of the paths with at least one row above its threshold
+                                                           (the paths counted on the device, divided on the host)
+    'exceed_probability' (n_rows,)                         share of the paths whose draw at the row is above its threshold
+  The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells, ValueError beyond.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  if num_samples > _native.SUMMARY_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the extremes are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
+                     'sample paths')
+  levels = [float(v) for v in quantiles]
+  if any(not 0.0 <= v <= 1.0 for v in levels):
+    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the matrices are held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  if threshold is not None:
+    threshold = np.ascontiguousarray(threshold, dtype=np.float64)
+    if threshold.shape != (n_rows,):
+      raise ValueError(f'threshold must hold one limit per row ({n_rows},); got {threshold.shape}')
+    if not np.all(np.isfinite(threshold)):
+      raise ValueError('threshold must be finite')
+  elif observed_count is not None:
+    raise ValueError('observed_count needs a threshold')
+  observed = {}
+  for name, obs in (('max', observed_max), ('count', observed_count)):
+    if obs is not None:
+      observed[name] = np.ascontiguousarray(obs, dtype=np.float64)
+      if observed[name].shape != (n_groups,):
+        raise ValueError(f'observed_{name} must hold one value per group ({n_groups},); got {observed[name].shape}')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
+  seed64 = _native.seed_to_u64(seed)
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    thr = None if threshold is None else threshold.astype(np.float32)
+    ext = eng.predictive_group_extremes(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
+                                        num_samples, seed64, threshold=thr, **kw)
+    out = {'peak_probability': ext['peak_count'].cpu().numpy().astype(np.float64) / num_samples}
+    for name in ('max', 'count') if thr is not None else ('max',):
+      y = torch.from_numpy(observed[name]).to(eng.device) if name in observed else None
+      for k, v in eng.sample_summaries(ext[name], y, levels).items():
+        out[f'{name}_{k}'] = v.cpu().numpy()
+    if thr is not None:
+      out['exceed_any'] = (ext['count'] > 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
+      out['exceed_probability'] = ext['exceed_count'].cpu().numpy().astype(np.float64) / num_samples
+    return out
+  finally:
+    eng.close()
+
+
 # ---------------------------------------------------------------------------
 # scores of held-out observations
 # ---------------------------------------------------------------------------

@@ -212,6 +212,34 @@ def group_target_sums(target, seg_offsets, seg_rows):
   return out
 
 
+def group_target_extremes(target, seg_offsets, seg_rows, threshold=None):
+  """Observed peaks: per group of the CSR layout `group_rows` returns, the largest `target` (R,) over the group's rows,
+  the lowest table row at which it is reached and, with `threshold` (R,), the number of rows whose target is > their
+  threshold -> (max (G,) float64, peak_row (G,) int64, count (G,) float64 or None).  A group with a NaN target among its
+  rows (and an empty one, which `group_rows` never makes) gives NaN, -1, NaN."""
+  target = np.asarray(target, dtype=np.float64)
+  order = np.asarray(seg_rows, dtype=np.int64)
+  sorted_target = target[order]
+  starts = np.asarray(seg_offsets[:-1], dtype=np.int64)
+  sizes = np.diff(np.asarray(seg_offsets, dtype=np.int64))
+  n_groups = len(starts)
+  peak = np.full(n_groups, np.nan)
+  peak_row = np.full(n_groups, -1, dtype=np.int64)
+  count = None if threshold is None else np.full(n_groups, np.nan)
+  full = sizes > 0
+  if sorted_target.size and full.any():
+    peak[full] = np.maximum.reduceat(sorted_target, starts[full])              # NaN if any row is NaN
+    group_of = np.repeat(np.arange(n_groups), sizes)
+    pos = np.arange(sorted_target.size, dtype=np.int64)
+    first = np.minimum.reduceat(np.where(sorted_target == peak[group_of], pos, sorted_target.size), starts[full])
+    seen = ~np.isnan(peak[full])
+    peak_row[np.flatnonzero(full)[seen]] = order[first[seen]]
+    if threshold is not None:
+      above = (sorted_target > np.asarray(threshold, dtype=np.float64)[order]).astype(np.float64)
+      count[full] = np.where(seen, np.add.reduceat(above, starts[full]), np.nan)
+  return peak, peak_row, count
+
+
 # ---------------------------------------------------------------------------
 # estimators
 # ---------------------------------------------------------------------------
@@ -435,7 +463,8 @@ class BayesianNeuralFieldEstimator:
       'equal_weight_mean_log_density' the same at equal weights: what `score(table)['mean_log_density']` reports
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
-    The weights are taken by `predict_samples`, `predict_totals` and `score_totals` (weights=...) and scored on
+    The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes` and `score_extremes`
+    (weights=...) and scored on
     another table by `weighted_log_density`; they are taken by the marginal forecast as well: `predict` and `score`
     (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.  `fit` is unchanged."""
     if self.params_ is None:
@@ -566,6 +595,97 @@ class BayesianNeuralFieldEstimator:
     out.update(keys=keys, observed=observed, n=int(scored.sum()))
     out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')
     return out
+
+  def _extreme_summaries(self, what, table, group_by, threshold, quantiles, num_samples, seed, target=None, weights=None):
+    if int(num_samples) < 1:
+      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
+    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{what}: num_samples={num_samples}: the extremes are summarised from at most '
+                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    thr = None
+    if threshold is not None:
+      try:
+        thr = np.asarray(threshold, dtype=np.float64)
+      except (TypeError, ValueError) as e:
+        raise ValueError(f'{what}: threshold must be a number or one number per row of the table') from e
+      if thr.ndim == 0:
+        thr = np.full(len(table), float(thr))
+      if thr.shape != (len(table),):
+        raise ValueError(f'{what}: threshold must be a scalar or hold one limit per row ({len(table)},); got {thr.shape}')
+      if not np.all(np.isfinite(thr)):
+        raise ValueError(f'{what}: threshold must be finite')
+      thr = thr.astype(np.float32).astype(np.float64)          # the draws are float32: compared at that precision
+    kw = self._weights_kw(weights)
+    keys, seg_offsets, seg_rows = group_rows(table, group_by)
+    observed = None if target is None else group_target_extremes(target, seg_offsets, seg_rows, thr)
+    rows = self.data_handler.get_test(table)
+    out = inference.extreme_summaries(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), threshold=thr,
+        observed_max=None if observed is None else observed[0], observed_count=None if observed is None else observed[2],
+        quantiles=tuple(quantiles), compute_dtype=self.compute_dtype, **kw)
+    res = {'keys': keys, 'max_mean': out['max_mean'], 'max_quantiles': out['max_quantiles'],
+           'peak_probability': out['peak_probability']}
+    if thr is not None:
+      res.update(exceed_any=out['exceed_any'], exceed_count_mean=out['count_mean'],
+                 exceed_count_quantiles=out['count_quantiles'], exceed_probability=out['exceed_probability'])
+    return res, out, observed
+
+  def predict_extremes(self, table, group_by, threshold=None, quantiles=(0.5,), num_samples=1000, seed=0, weights=None):
+    """Group peaks and threshold exceedances of the sample paths of `predict_samples(table, num_samples, seed)`, formed
+    and summarised on the GPU: neither the draws nor the (num_samples, G) matrices leave the device.  What no marginal
+    quantile of `predict` gives: the maximum and the count of a path depend on one member driving all rows.  -> dict:
+      'keys'                    the groups, as in `predict_samples`
+      'max_mean' (G,)  'max_quantiles' (len(quantiles), G)   the distribution of the group's peak value ('linear' quantiles)
+      'peak_probability' (len(table),)   the share of the paths in which the row is where its group first reaches its
+                                maximum (ties, frequent for counts, go to the group's first row in table order): sums to 1
+                                over the rows of every group
+    and with `threshold`, a scalar or one finite limit per row, in the units of the target column, compared with strict >
+    at float32 precision (the precision of the draws):
+      'exceed_any' (G,)         the share of the paths with at least one row of the group above its threshold
+      'exceed_count_mean' (G,)  'exceed_count_quantiles' (len(quantiles), G)   the number of rows of the group above
+      'exceed_probability' (len(table),)   the share of the paths whose draw at the row is above its threshold
+    num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    if self.params_ is None:
+      raise ValueError('predict_extremes before fit')
+    res, _, _ = self._extreme_summaries('predict_extremes', table, group_by, threshold, quantiles, num_samples, seed,
+                                        weights=weights)
+    return res
+
+  def score_extremes(self, table, group_by, threshold=None, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0,
+                     weights=None):
+    """The forecast of `predict_extremes` scored against the peaks and exceedances observed in `table[target_col]`, on
+    the GPU.  -> the dict of `predict_extremes` plus
+      'observed_max' (G,)  'observed_peak_row' (G,)   the largest target of the group and the first table row (position)
+                                at which it is reached; NaN / -1 when any row of the group has a NaN target: such a
+                                group is not scored
+      'max_crps' (G,)  'max_pit' (2, G)   ensemble CRPS of the peak value and the share of the sampled peaks <= and < the
+                                observed one; NaN where not scored
+      'peak_row_probability' (G,)   the forecast probability ('peak_probability') of the observed peak row
+      'n'                       number of groups scored       'mean_max_crps', 'mean_peak_row_probability'  means over them
+    and with `threshold`:
+      'observed_count' (G,)     the rows of the group whose target is > their threshold
+      'count_crps' (G,)  'count_pit' (2, G)   the same scores of the number of rows above
+      'brier' (G,)              (exceed_any - 1{observed_count > 0})^2
+      'mean_count_crps', 'mean_brier'
+    The target checks are those of `score_totals`."""
+    if self.params_ is None:
+      raise ValueError('score_extremes before fit')
+    y = self._targets('score_extremes', table)
+    res, out, (obs_max, obs_row, obs_count) = self._extreme_summaries(
+        'score_extremes', table, group_by, threshold, quantiles, num_samples, seed, target=y, weights=weights)
+    scored = ~np.isnan(obs_max)
+    mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
+    prob = np.where(scored, res['peak_probability'][np.maximum(obs_row, 0)], np.nan)
+    res.update(observed_max=obs_max, observed_peak_row=obs_row, max_crps=out['max_crps'], max_pit=out['max_pit'],
+               peak_row_probability=prob, n=int(scored.sum()), mean_max_crps=mean(out['max_crps']),
+               mean_peak_row_probability=mean(prob))
+    if obs_count is not None:
+      hit = np.where(scored, (obs_count > 0).astype(np.float64), np.nan)
+      brier = (res['exceed_any'] - hit) ** 2
+      res.update(observed_count=obs_count, count_crps=out['count_crps'], count_pit=out['count_pit'], brier=brier,
+                 mean_count_crps=mean(out['count_crps']), mean_brier=mean(brier))
+    return res
 
   def likelihood_model(self, table):
     """Predictive distribution of every member at the rows of `table`

@@ -324,6 +324,38 @@ int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const fl
                                        int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
                                        const double* cum_weights, void* work, size_t work_bytes, double* out);
 
+/* PEAKS and threshold EXCEEDANCES of the same sample paths over groups of rows, without materialising the draws (the
+ * reference has no counterpart: it would reduce `.sample()` on the host).  The value at (path s, row r) is the f32 that
+ * bnf_predictive_samples writes for (seed, sample0 + s, row0 + r), bit for bit; loc, aux, seg_offsets, seg_rows, row0,
+ * sample0 as for bnf_predictive_group_sums.  Per (path s, group g):
+ *   out_max DEVICE (n_samples, n_groups) f64: the largest draw over the group's rows (the f32 draw widened: the matrix
+ *     is one bnf_sample_summaries takes)
+ *   out_argmax DEVICE (n_samples, n_groups) int32 or NULL: the TABLE ROW (an entry of seg_rows) at which that maximum is
+ *     first reached.  Tie rule: among equal draws the lowest position of seg_rows wins -- the lowest table row of the
+ *     group when the rows ascend inside a group
+ *   out_count DEVICE (n_samples, n_groups) f64, NULL iff threshold is NULL: the number of rows of the group whose draw is
+ *     strictly greater than threshold[row] (an exact integer)
+ *   threshold DEVICE (n_rows,) f32 or NULL: one limit per table row, in the units of the draws
+ *   cum_weights DEVICE (n_members,) f64 or NULL: as for bnf_predictive_samples_weighted; NULL takes the integer
+ *     floor(u n_members) component of the equal-weight calls
+ * NaN rule: a NaN draw enters the maximum as -inf (at its own position) and never exceeds a threshold, so "b beats a iff
+ * b.v > a.v, or b.v == a.v and b.pos < a.pos" is a total order and the result does not depend on tile edges, the launch
+ * geometry or the number of passes.  Entries of seg_rows outside [0, n_rows) take no part.  Empty-group values: a group
+ * without a row that takes part reports max = NaN, argmax = -1, count = 0.
+ * Two optional per-row counters, DEVICE (n_rows,) uint32, ZEROED BY THE CALLER and added to with integer atomics only:
+ *   peak_count[r] += the number of paths in which row r is its group's argmax
+ *   exceed_count[r] += the number of paths whose draw at r is > threshold[r] (needs threshold)
+ *   work DEVICE, work_bytes: per-tile pieces, BNF_EXTREMES_WORK_PER_TILE bytes x ceil(n_rows / BNF_GROUP_TILE) per sample
+ *     path; the samples are processed in as many passes as the buffer asks for (BNF_ERR_INVALID below one path's worth)
+ * Deterministic: no floating-point atomics -- two calls give the same bits.  Runs on the handle's stream, does not touch
+ * the training state, works on forward-only handles. */
+#define BNF_EXTREMES_WORK_PER_TILE 32
+int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
+                                  const float* threshold, void* work, size_t work_bytes, double* out_max,
+                                  int32_t* out_argmax, double* out_count, uint32_t* peak_count, uint32_t* exceed_count);
+
 /* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
  * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
  * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
