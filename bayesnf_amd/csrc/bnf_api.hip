@@ -37,6 +37,7 @@
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
+#include "bnf_dependence.h"
 #include "bnf_stacking.h"
 
 using namespace bnf;
@@ -2385,6 +2386,53 @@ int bnf_sample_energy_score(bnf_handle* h, const double* x, int64_t n_samples, i
                      (double*)work);
   hipLaunchKernelGGL(k_energy_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, n_samples,
                      nT * (nT + 1) / 2, y, n_cols, out);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- covariance, variogram and variogram score of sample paths (bnf_dependence.h) ------
+int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, double p, const double* y,
+                            const double* pair_w, double* mean, double* cov, double* vario, void* work, size_t work_bytes,
+                            double* score) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!x || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  const int form = p == 0.5 ? 0 : p == 1.0 ? 1 : p == 2.0 ? 2 : -1;
+  if (form < 0) return fail(BNF_ERR_INVALID, "p = %g: the variogram is compiled for p = 0.5, 1 and 2", p);
+  if ((cov || vario || pair_w) && n_cols > BNF_PAIR_MATRIX_MAX_COLS)
+    return fail(BNF_ERR_INVALID, "%lld columns: a pair matrix has at most %d a side", (long long)n_cols,
+                BNF_PAIR_MATRIX_MAX_COLS);
+  const int64_t nT = pair_tiles(n_cols);
+  if (nT > 65535) return fail(BNF_ERR_INVALID, "%lld columns: at most %d pair tiles a side", (long long)n_cols, 65535);
+  if (cov && !mean) return fail(BNF_ERR_INVALID, "cov needs mean: the centred products read it");
+  if (score) {
+    if (!y) return fail(BNF_ERR_INVALID, "score needs the observations y");
+    const size_t need = sizeof(double) * (size_t)pair_work_doubles(n_cols);
+    if (!work || work_bytes < need)
+      return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld columns need %zu", work ? work_bytes : (size_t)0,
+                  (long long)n_cols, need);
+  }
+  if (!mean && !cov && !vario && !score) return BNF_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (mean)
+    hipLaunchKernelGGL(k_column_means, dim3((unsigned)((n_cols + kDpMeanCols - 1) / kDpMeanCols)),
+                       dim3(kDpMeanCols * kDpMeanLanes), 0, h->stream, x, n_samples, n_cols, mean);
+  if (cov || vario || score) {
+    double* partials = score ? (double*)work : nullptr;
+    const double* yy = score ? y : nullptr;
+    const double* ww = score ? pair_w : nullptr;
+    if (!vario && !score)                              // the covariance alone: p plays no part
+      launch_pair_moments<2>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
+    else if (form == 0)
+      launch_pair_moments<0>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
+    else if (form == 1)
+      launch_pair_moments<1>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
+    else
+      launch_pair_moments<2>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
+    if (score)
+      hipLaunchKernelGGL(k_vario_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, nT * (nT + 1) / 2, y,
+                         n_cols, score);
+  }
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

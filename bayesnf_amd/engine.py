@@ -606,6 +606,45 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work` is released on return
     return float(out.cpu()[0])
 
+  def sample_pair_moments(self, x, p=0.5, y=None, pair_weights=None, matrices=True) -> dict:
+    """How the columns of the joint paths x (S, G) f64 move together (include/bnf.h bnf_sample_pair_moments) -> dict of
+    f64 device tensors:
+      'mean' (G,)
+      'covariance' (G, G)   matrices=True: (1 / S) sum_s (x_si - m_i) (x_sj - m_j), np.cov(x.T, bias=True)
+      'variogram' (G, G)    matrices=True: (1 / S) sum_s |x_si - x_sj|^p
+    and with the observed vector y (G,)
+      'variogram_score' float   sum over the pairs i < j with y_i, y_j not NaN of w_ij (|y_i - y_j|^p - variogram_ij)^2,
+                                w_ij = 1 or pair_weights (G, G) (read above the diagonal)
+    p is 0.5, 1 or 2.  Both matrices are whole and bitwise symmetric; matrices=False writes nothing of size G^2 and gives
+    the same score bits.  matrices / pair_weights with G > BNF_PAIR_MATRIX_MAX_COLS is a ValueError, as is another p (the
+    library's error).  S G^2 / 2 pair terms.  Deterministic."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, G = x.shape
+    y = None if y is None else self._as_f64(y, (G,), 'y')
+    if pair_weights is not None and y is None:
+      raise ValueError('pair_weights weight the variogram score: they need y')
+    if (matrices or pair_weights is not None) and G > _native.PAIR_MATRIX_MAX_COLS:
+      raise ValueError(f'{G} columns: a pair matrix (matrices, pair_weights) has at most {_native.PAIR_MATRIX_MAX_COLS} '
+                       'a side')
+    w = None if pair_weights is None else self._as_f64(pair_weights, (G, G), 'pair_weights')
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+    out = {'mean': f64(G)}
+    if matrices:
+      out['covariance'], out['variogram'] = f64(G, G), f64(G, G)
+    n_work = _native.pair_work_doubles(G) if y is not None else 0
+    work = f64(n_work) if y is not None else None
+    score = f64(1) if y is not None else None
+    _native.check(self.lib.bnf_sample_pair_moments(
+        self.handle, _ptr(x), S, G, C.c_double(float(p)), _ptr(y), _ptr(w), _ptr(out['mean']),
+        _ptr(out.get('covariance')), _ptr(out.get('variogram')), _ptr(work), C.c_size_t(n_work * 8), _ptr(score)),
+        'bnf_sample_pair_moments')
+    torch.cuda.synchronize(self.device)     # `work` and the device copies made here are released on return
+    if y is not None:
+      out['variogram_score'] = float(score.cpu()[0])
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

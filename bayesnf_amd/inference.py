@@ -456,6 +456,80 @@ def total_summaries(features, observation_model, params, model_args, num_samples
     eng.close()
 
 
+VARIOGRAM_ORDERS = (0.5, 1.0, 2.0)      # the p the variogram is compiled for (include/bnf.h bnf_sample_pair_moments)
+
+
+def dependence_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                         observed=None, p=0.5, pair_weights=None, matrices=True, compute_dtype=None, weights=None):
+  """How the group totals of the joint sample paths move together, formed and scored on the GPU: the (num_samples, G)
+  matrix `sample_predictive(..., groups=groups)` would return stays on the device (include/bnf.h
+  bnf_predictive_group_sums) and only the results come back (bnf_sample_pair_moments).  groups = (seg_offsets, seg_rows) as
+  `csr_from_codes` builds them; observed (G,) the observed totals, NaN where a group is not to be scored.
+  -> dict of float64 numpy arrays:
+    'mean' (G,)
+    'covariance' (G, G)  'variogram' (G, G)   matrices=True: (1 / S) sum_s (x_si - m_i) (x_sj - m_j) -- np.cov(bias=True)
+                                              -- and (1 / S) sum_s |x_si - x_sj|^p, both bitwise symmetric
+    'variogram_score' float                   with `observed`: sum over the pairs i < j of scored groups of
+                                              w_ij (|y_i - y_j|^p - variogram_ij)^2, w_ij = 1 or pair_weights[i][j]
+  p is 0.5, 1 or 2; pair_weights (G, G) finite, >= 0 and symmetric.  num_samples * G <= 2^28 cells (there is no cap on the
+  sample paths alone: nothing is sorted), and G <= 4,096 with `matrices` or `pair_weights`; ValueError beyond, before any
+  GPU work.  num_samples G^2 / 2 pair terms.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  try:
+    p = float(p)
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'p must be one of {VARIOGRAM_ORDERS}') from e
+  if p not in VARIOGRAM_ORDERS:
+    raise ValueError(f'p={p!r}: the variogram is formed for p in {VARIOGRAM_ORDERS}')
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+  if (matrices or pair_weights is not None) and n_groups > _native.PAIR_MATRIX_MAX_COLS:
+    raise ValueError(f'{n_groups} groups: a pair matrix (matrices=True, pair_weights) has at most '
+                     f'{_native.PAIR_MATRIX_MAX_COLS} groups a side; matrices=False gives the variogram score alone')
+  if observed is not None:
+    observed = np.ascontiguousarray(observed, dtype=np.float64)
+    if observed.shape != (n_groups,):
+      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  if pair_weights is not None:
+    if observed is None:
+      raise ValueError('pair_weights weight the variogram score: they need `observed`')
+    try:
+      pair_weights = np.ascontiguousarray(pair_weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'pair_weights must be an array of numbers of shape ({n_groups}, {n_groups})') from e
+    if pair_weights.shape != (n_groups, n_groups):
+      raise ValueError(f'pair_weights must hold one weight per pair of groups ({n_groups}, {n_groups}); got '
+                       f'{pair_weights.shape}')
+    if not np.all(np.isfinite(pair_weights)):
+      raise ValueError('pair_weights must be finite')
+    if np.any(pair_weights < 0):
+      raise ValueError('pair_weights must be >= 0')
+    if not np.array_equal(pair_weights, pair_weights.T):
+      raise ValueError('pair_weights must be symmetric')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
+  seed64 = _native.seed_to_u64(seed)
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
+                                       num_samples, seed64, **kw)
+    y = None if observed is None else torch.from_numpy(observed).to(eng.device)
+    w = None if pair_weights is None else torch.from_numpy(pair_weights).to(eng.device)
+    res = eng.sample_pair_moments(totals, p, y, w, matrices=bool(matrices))
+    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in res.items()}
+  finally:
+    eng.close()
+
+
 def extreme_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
                       threshold=None, observed_max=None, observed_count=None, quantiles=(), compute_dtype=None,
                       weights=None):

@@ -463,8 +463,8 @@ class BayesianNeuralFieldEstimator:
       'equal_weight_mean_log_density' the same at equal weights: what `score(table)['mean_log_density']` reports
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
-    The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes` and `score_extremes`
-    (weights=...) and scored on
+    The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
+    `predict_dependence` and `score_dependence` (weights=...) and scored on
     another table by `weighted_log_density`; they are taken by the marginal forecast as well: `predict` and `score`
     (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.  `fit` is unchanged."""
     if self.params_ is None:
@@ -685,6 +685,87 @@ class BayesianNeuralFieldEstimator:
       brier = (res['exceed_any'] - hit) ** 2
       res.update(observed_count=obs_count, count_crps=out['count_crps'], count_pit=out['count_pit'], brier=brier,
                  mean_count_crps=mean(out['count_crps']), mean_brier=mean(brier))
+    return res
+
+  def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=None, p=0.5,
+                            pair_weights=None, matrices=True):
+    if int(num_samples) < 1:
+      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
+    kw = self._weights_kw(weights)
+    keys, seg_offsets, seg_rows = group_rows(table, group_by)
+    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
+    rows = self.data_handler.get_test(table)
+    out = inference.dependence_summaries(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, p=p,
+        pair_weights=pair_weights, matrices=bool(matrices), compute_dtype=self.compute_dtype, **kw)
+    res = {'keys': keys, 'mean': out['mean']}
+    if 'covariance' in out:
+      cov = out['covariance']
+      std = np.sqrt(np.diagonal(cov))
+      flat = ~(std > 0)                             # a group without spread (or NaN) has no correlation
+      with np.errstate(divide='ignore', invalid='ignore'):
+        corr = cov / (std[:, None] * std[None, :])
+      corr[flat, :] = np.nan
+      corr[:, flat] = np.nan
+      res.update(std=std, covariance=cov, correlation=corr)
+    return res, out, observed
+
+  def predict_dependence(self, table, group_by, num_samples=1000, seed=0, weights=None):
+    """How the group totals of `predict_samples(table, num_samples, seed, group_by=group_by)` move together -- "if group A
+    has a bad week, how likely is it that group B does too" -- formed on the GPU: the (num_samples, G) matrix of totals
+    never leaves the device.  The sample paths are joint (one member drives all rows of a path), so the totals of
+    different groups are dependent; no marginal forecast shows it.  -> dict:
+      'keys'               the groups, as in `predict_samples`
+      'mean' (G,)          'std' (G,)   mean and standard deviation of the sampled totals (std: sqrt of the diagonal below)
+      'covariance' (G, G)  (1 / S) sum_s (x_sg - mean_g) (x_sh - mean_h) over the S = num_samples paths: the ensemble's own
+                           moment, np.cov(totals.T, bias=True), bitwise symmetric
+      'correlation' (G, G) covariance_gh / (std_g std_h), formed on the host; NaN in the row and column of a group whose
+                           std is 0, 1 on the rest of the diagonal
+    At most 4,096 groups, and num_samples * G <= 2^28.  weights: member weights of the sample paths as in
+    `predict_samples`; None: equal weights."""
+    if self.params_ is None:
+      raise ValueError('predict_dependence before fit')
+    res, _, _ = self._dependence_summaries('predict_dependence', table, group_by, num_samples, seed, weights)
+    return res
+
+  def score_dependence(self, table, group_by, p=0.5, pair_weights=None, matrices=True, num_samples=1000, seed=0,
+                       weights=None):
+    """The co-movement of the group totals scored against the totals observed in `table[target_col]`, on the GPU: the
+    variogram score of order p (Scheuerer & Hamill 2015), the companion of `score_totals(...)['energy_score']`, which is
+    nearly blind to a wrong correlation structure.  p is 0.5, 1 or 2.  -> the dict of `predict_dependence` ('std',
+    'covariance', 'correlation' with matrices=True only) plus
+      'observed' (G,)             sum of the target over the group's rows; NaN when any row of the group has a NaN target:
+                                  such a group is in no scored pair
+      'variogram' (G, G)          matrices=True: (1 / S) sum_s |x_sg - x_sh|^p over the sample paths
+      'observed_variogram' (G, G) matrices=True: |observed_g - observed_h|^p; NaN where not scored
+      'variogram_score'           sum over the pairs g < h of scored groups of w_gh (observed_variogram_gh - variogram_gh)^2;
+                                  w_gh = 1, or pair_weights (G, G), finite, >= 0 and symmetric (e.g. decaying with the
+                                  distance between two places); lower is better
+      'n', 'n_pairs'              groups scored and n (n - 1) / 2
+      'mean_variogram_score'      'variogram_score' / the sum of the weights of the scored pairs; NaN for n_pairs = 0
+    matrices=False returns the score alone and lifts the cap of 4,096 groups (pair_weights keep it);
+    num_samples * G <= 2^28 either way.  The target checks are those of `score_totals`.  weights: member weights of the
+    sample paths as in `predict_samples`; None: equal weights."""
+    if self.params_ is None:
+      raise ValueError('score_dependence before fit')
+    y = self._targets('score_dependence', table)
+    res, out, observed = self._dependence_summaries(
+        'score_dependence', table, group_by, num_samples, seed, weights, target=y, p=p, pair_weights=pair_weights,
+        matrices=matrices)
+    scored = ~np.isnan(observed)
+    n = int(scored.sum())
+    res.update(observed=observed, variogram_score=out['variogram_score'], n=n, n_pairs=n * (n - 1) // 2)
+    if 'variogram' in out:
+      d = np.abs(observed[:, None] - observed[None, :])
+      res.update(variogram=out['variogram'],
+                 observed_variogram=np.sqrt(d) if float(p) == 0.5 else d if float(p) == 1.0 else d * d)
+    if pair_weights is None:
+      total = float(res['n_pairs'])
+    else:
+      w = np.asarray(pair_weights, dtype=np.float64)[np.ix_(scored, scored)]
+      total = float(np.sum(np.triu(w, 1), dtype=np.float64))
+    res['mean_variogram_score'] = res['variogram_score'] / total if res['n_pairs'] > 0 and total > 0 else float('nan')
     return res
 
   def likelihood_model(self, table):

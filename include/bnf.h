@@ -510,6 +510,37 @@ int bnf_sample_summaries(bnf_handle* h, const double* x, int64_t n_samples, int6
 int bnf_sample_energy_score(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
                             void* work, size_t work_bytes, double* out);
 
+/* The DEPENDENCE between the columns of the joint sample paths: their predictive covariance, their variogram, and the
+ * variogram score of order p (Scheuerer & Hamill 2015) against the observed vector -- the companion of the energy score,
+ * which is nearly blind to a wrong correlation structure.  x as for bnf_sample_summaries, S = n_samples, G = n_cols.
+ *   mean DEVICE (G,) f64: m_c = (1 / S) sum_s x_sc
+ *   cov DEVICE (G, G) f64: cov[i][j] = (1 / S) sum_s (x_si - m_i) (x_sj - m_j), from centred products (a total of 1e9 with
+ *     a spread of 10 loses nothing); the divisor is S, the ensemble's own moment: np.cov(x.T, bias=True).  Needs mean.
+ *   vario DEVICE (G, G) f64: vario[i][j] = (1 / S) sum_s |x_si - x_sj|^p
+ *   score DEVICE (1,) f64: sum over the pairs i < j with y_i and y_j finite of w_ij (|y_i - y_j|^p - vario[i][j])^2, with
+ *     y DEVICE (G,) f64 the observed totals and w_ij = 1, or pair_w[i][j] from pair_w DEVICE (G, G) f64 (read above the
+ *     diagonal only; not validated: reading it would cost a sync).  Fewer than two finite y_c: NaN.
+ *   p is 0.5, 1 or 2, compiled as sqrt(fabs d), fabs d and d * d; any other p is BNF_ERR_INVALID.
+ * y, pair_w, mean, cov, vario and score may each be NULL: a NULL output is skipped, and with cov and vario NULL nothing of
+ * size G^2 is written.  score needs y (BNF_ERR_INVALID without) and
+ *   work DEVICE, work_bytes: one partial sum per BNF_PAIR_COL_TILE x BNF_PAIR_COL_TILE tile of pairs on or above the
+ *     diagonal, 8 * T (T + 1) / 2 bytes, T = ceil(G / BNF_PAIR_COL_TILE); BNF_ERR_INVALID below that.  Not read otherwise.
+ * Both matrices are written whole and are bitwise symmetric; vario[i][i] and the cell of two identical columns are exactly
+ * 0.  A cell's bits depend on S and on its two columns only, not on G or on the other columns of the call: every cell is
+ * one sequential sum over the paths (which stream through LDS BNF_PAIR_PATH_CHUNK at a time).  A column holding a NaN
+ * sample is NaN in its row and column of both matrices, and makes the score NaN when its y_c is finite (whatever its
+ * weights: w_ij is a plain factor).  The cost is S G^2 / 2 pair terms.  cov, vario or pair_w with
+ * G > BNF_PAIR_MATRIX_MAX_COLS (a matrix of 128 MiB), n_samples < 1 and n_cols < 1 are BNF_ERR_INVALID; there is no cap on
+ * n_samples (nothing is sorted).  Everything is f64, every sum in an order the shapes fix: no atomics, two calls give the
+ * same bits.  Runs on the handle's stream, does not touch the training state, works on forward-only handles; the
+ * observation model of the handle plays no part. */
+#define BNF_PAIR_COL_TILE 64
+#define BNF_PAIR_PATH_CHUNK 32
+#define BNF_PAIR_MATRIX_MAX_COLS 4096
+int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, double p, const double* y,
+                            const double* pair_w, double* mean, double* cov, double* vario, void* work, size_t work_bytes,
+                            double* score);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
