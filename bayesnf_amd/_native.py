@@ -29,6 +29,7 @@ SUMMARY_MAX_SAMPLES, SUMMARY_MAX_QUANTILES, ENERGY_SAMPLE_TILE = 16384, 64, 64
 PAIR_COL_TILE, PAIR_PATH_CHUNK, PAIR_MATRIX_MAX_COLS = 64, 32, 4096
 GROUP_TILE = 1024   # BNF_GROUP_TILE: rows per partial sum of bnf_predictive_group_sums (sizes its work buffer)
 EXTREMES_WORK_PER_TILE = 32   # BNF_EXTREMES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_extremes' work buffer
+EPISODES_WORK_PER_TILE = 80   # BNF_EPISODES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_episodes' work buffer
 STACK_ROW_TILE, STACK_STATE_DOUBLES = 1024, 8   # BNF_STACK_*: size the work buffer of bnf_stacking_weights
 
 
@@ -63,7 +64,7 @@ EXPORTS = (
     'bnf_member_log_density', 'bnf_stacking_weights', 'bnf_predictive_samples_weighted',
     'bnf_predictive_group_sums_weighted', 'bnf_normal_mixture_quantiles_weighted',
     'bnf_count_mixture_quantiles_weighted', 'bnf_predictive_scores_weighted', 'bnf_count_rps_weighted',
-    'bnf_predictive_group_extremes', 'bnf_sample_pair_moments',
+    'bnf_predictive_group_extremes', 'bnf_sample_pair_moments', 'bnf_predictive_group_episodes',
     'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
@@ -158,6 +159,8 @@ def load():
   lib.bnf_predictive_group_sums.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, C.c_size_t, vp]
   lib.bnf_predictive_group_extremes.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp, vp,
                                                 C.c_size_t, vp, vp, vp, vp, vp]
+  lib.bnf_predictive_group_episodes.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp, vp,
+                                                C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
   lib.bnf_predictive_scores.argtypes = [vp, vp, vp, i64, i64, vp, vp, C.c_size_t, vp, vp, vp, vp]
   lib.bnf_count_rps.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_sample_summaries.argtypes = [vp, vp, i64, i64, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]

@@ -34,6 +34,7 @@
 #include "bnf_gemm8.h"
 #include "bnf_sampling.h"
 #include "bnf_extremes.h"
+#include "bnf_episodes.h"
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
@@ -1410,6 +1411,21 @@ static void launch_predictive_group_extremes(bnf_handle* h, const float* loc, co
                      seg_offsets, (int32_t)G, R, S, partial, o);
 }
 
+// spells above a threshold in the same paths (bnf_episodes.h): the launch shape of the group sums
+template <int OBS>
+static void launch_predictive_group_episodes(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
+                                             const int32_t* seg_offsets, int64_t G, int64_t S, uint64_t seed, int64_t row0,
+                                             int64_t sample0, const double* cum, const float* threshold, EpPiece* partial,
+                                             const EpOut& o) {
+  const int64_t nt = cdiv(R, kPredTile);
+  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
+  hipLaunchKernelGGL((k_predictive_group_episodes<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc,
+                     aux, (int32_t)M, R, seg_offsets, o.seg_rows, (int32_t)G, S, seed, row0, sample0, cum, threshold,
+                     partial, o);
+  hipLaunchKernelGGL(k_predictive_group_episodes_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
+                     seg_offsets, (int32_t)G, R, S, partial, o);
+}
+
 // held-out scoring launches (bnf_scoring.h), one instantiation per observation model and for the member weights wts
 // (WEIGHTED: wts non-null, no member_ll)
 template <int OBS, bool WEIGHTED>
@@ -2160,6 +2176,48 @@ int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* 
       case BNF_OBS_NORMAL: launch_predictive_group_extremes<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
       case BNF_OBS_NB: launch_predictive_group_extremes<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
       default: launch_predictive_group_extremes<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- spells above a threshold in the sample paths (bnf_episodes.h) ----
+int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
+                                  const float* threshold, void* work, size_t work_bytes, double* out_longest,
+                                  int32_t* out_longest_row, double* out_spells, double* out_onset_step,
+                                  int32_t* out_first_row, int32_t* out_last_row, uint32_t* onset_count) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || !work || n_groups < 1 || n_groups > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (!threshold || !out_longest) return fail(BNF_ERR_INVALID, "threshold and out_longest are required");
+  const int64_t nt = cdiv(n_rows, kPredTile);
+  const size_t per_sample = (size_t)nt * BNF_EPISODES_WORK_PER_TILE;
+  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
+  if (chunk < 1)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
+                (long long)n_rows, per_sample);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // groups without a row: 0 / -1 / 0 / 0 / -1 / -1
+  const size_t cells = (size_t)n_samples * (size_t)n_groups;
+  HIPCHK(hipMemsetAsync(out_longest, 0, cells * sizeof(double), h->stream));
+  if (out_longest_row) HIPCHK(hipMemsetAsync(out_longest_row, 0xff, cells * sizeof(int32_t), h->stream));
+  if (out_spells) HIPCHK(hipMemsetAsync(out_spells, 0, cells * sizeof(double), h->stream));
+  if (out_onset_step) HIPCHK(hipMemsetAsync(out_onset_step, 0, cells * sizeof(double), h->stream));
+  if (out_first_row) HIPCHK(hipMemsetAsync(out_first_row, 0xff, cells * sizeof(int32_t), h->stream));
+  if (out_last_row) HIPCHK(hipMemsetAsync(out_last_row, 0xff, cells * sizeof(int32_t), h->stream));
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
+    const int64_t n = std::min(chunk, n_samples - s0);
+    const int64_t at = s0 * n_groups;
+    const EpOut o{seg_rows, out_longest + at, out_longest_row ? out_longest_row + at : nullptr,
+                  out_spells ? out_spells + at : nullptr, out_onset_step ? out_onset_step + at : nullptr,
+                  out_first_row ? out_first_row + at : nullptr, out_last_row ? out_last_row + at : nullptr, onset_count};
+    switch (h->cfg.obs_model) {
+      case BNF_OBS_NORMAL: launch_predictive_group_episodes<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
+      case BNF_OBS_NB: launch_predictive_group_episodes<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
+      default: launch_predictive_group_episodes<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
     }
   }
   HIPCHK(hipGetLastError());

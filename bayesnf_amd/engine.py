@@ -420,6 +420,57 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work`, `off`, `rows`, `thr` and `cum` are released on return
     return out
 
+  def predictive_group_episodes(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
+                                threshold, cum_weights=None, per_row=True, row0=0, sample0=0) -> dict:
+    """Spells above a threshold in the same sample paths, per group of rows (include/bnf.h
+    bnf_predictive_group_episodes), without materialising the draws; loc, aux, seg_offsets, seg_rows, row0, sample0 and
+    cum_weights as for `predictive_group_sums`.  TIME is the order of the positions of seg_rows inside a group
+    (`inference.csr_ordered`).  threshold (R,) f32, one limit per table row: a position exceeds when its draw is > its
+    limit; a NaN draw does not exceed but breaks a spell and counts as a step; an entry of seg_rows outside [0, R) takes
+    no part.  -> dict of device tensors:
+      'longest' (n_samples, G) f64        length of the longest run of consecutive exceeding positions, 0 if none
+      'longest_row' (n_samples, G) int32  the table row at which it starts (the earliest of equally long runs), -1 if none
+      'spells' (n_samples, G) f64         the number of maximal runs
+      'onset_step' (n_samples, G) f64     participating positions before the first exceeding one; all of them if none
+      'first_row', 'last_row' (n_samples, G) int32   table row of the first / last exceeding position, -1 if none
+      'onset_count' (R,) int32            per_row=True: the paths in which the row is its group's first exceeding row
+    Deterministic: the same call gives the same bits."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+                        ).to(self.device, dtype=torch.int32).contiguous()
+    off, rows = as_i32(seg_offsets), as_i32(seg_rows)
+    G = off.numel() - 1
+    if G < 1 or rows.numel() != R:
+      raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
+    if threshold is None:
+      raise ValueError('threshold is required: one limit per row')
+    thr = (threshold if isinstance(threshold, torch.Tensor)
+           else torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32))).to(self.device, dtype=torch.float32).contiguous()
+    if tuple(thr.shape) != (R,):
+      raise ValueError(f'threshold must hold one limit per row ({R},); got {tuple(thr.shape)}')
+    n_samples = int(n_samples)
+    f64 = lambda: torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+    i32 = lambda: torch.empty((n_samples, G), dtype=torch.int32, device=self.device)
+    out = {'longest': f64(), 'longest_row': i32(), 'spells': f64(), 'onset_step': f64(), 'first_row': i32(),
+           'last_row': i32()}
+    if per_row:                             # the library adds to it: zeroed here
+      out['onset_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+    # per-tile pieces: BNF_EPISODES_WORK_PER_TILE bytes per tile and path, at most ~64 MB (the library makes several
+    # passes beyond that)
+    per_path = _native.EPISODES_WORK_PER_TILE * (-(-R // _native.GROUP_TILE))
+    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // per_path)), dtype=torch.uint8, device=self.device)
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_group_episodes(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(thr), _ptr(work),
+        C.c_size_t(work.numel()), _ptr(out['longest']), _ptr(out['longest_row']), _ptr(out['spells']),
+        _ptr(out['onset_step']), _ptr(out['first_row']), _ptr(out['last_row']), _ptr(out.get('onset_count'))),
+        'bnf_predictive_group_episodes')
+    torch.cuda.synchronize(self.device)     # `work`, `off`, `rows`, `thr` and `cum` are released on return
+    return out
+
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
                         lpd=True, pit=True, weights=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),

@@ -332,6 +332,27 @@ def csr_from_codes(codes, n_groups):
   return seg_offsets.astype(np.int32), seg_rows.astype(np.int32)
 
 
+def csr_ordered(codes, n_groups, key):
+  """`csr_from_codes` with the rows of every group in the order of `key` (R,), a sortable numeric or datetime array:
+  ascending, rows with equal keys in table order (the sort is stable).  The layout `bnf_predictive_group_episodes` reads
+  as time: position order inside a group.  -> (seg_offsets (n_groups + 1,) int32, seg_rows (R,) int32)."""
+  seg_offsets, _ = csr_from_codes(codes, n_groups)
+  codes = np.asarray(codes)
+  key = np.asarray(key)
+  if key.shape != codes.shape:
+    raise ValueError(f'the order key must hold one value per row {codes.shape}; got {key.shape}')
+  if key.dtype.kind in 'mM':
+    if np.isnat(key).any():
+      raise ValueError('the order key holds missing values')
+    key = key.view(np.int64)
+  elif key.dtype.kind not in 'biuf':
+    raise ValueError(f'the order key must be numeric or datetime; got dtype {key.dtype}')
+  elif key.dtype.kind == 'f' and np.isnan(key).any():
+    raise ValueError('the order key holds missing values')
+  seg_rows = np.lexsort((key, codes))          # by group, then by key; lexsort is stable
+  return seg_offsets, seg_rows.astype(np.int32)
+
+
 def mixture_weights(weights, params, ensemble_dims):
   """Member weights checked and flattened: `weights` must have the shape of the leading ensemble dims of `params` (what
   `member_log_prob` of score_predictive has; for VI the posterior draws count as components), every entry finite and >= 0,
@@ -597,6 +618,79 @@ def extreme_summaries(features, observation_model, params, model_args, num_sampl
     if thr is not None:
       out['exceed_any'] = (ext['count'] > 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
       out['exceed_probability'] = ext['exceed_count'].cpu().numpy().astype(np.float64) / num_samples
+    return out
+  finally:
+    eng.close()
+
+
+EPISODE_SERIES = ('longest', 'spells', 'onset_step')
+
+
+def episode_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                      threshold, observed_longest=None, observed_spells=None, observed_onset_step=None, quantiles=(),
+                      compute_dtype=None, weights=None):
+  """Spells above a threshold in the joint sample paths, summarised and scored on the GPU: per path and group the
+  longest run of consecutive rows above their threshold, the number of runs and the number of steps before the first row
+  above are formed without materialising the draws (include/bnf.h bnf_predictive_group_episodes); the (num_samples, G)
+  matrices stay on the device and go through bnf_sample_summaries.  groups = (seg_offsets, seg_rows) with the rows of a
+  group in TIME order (`csr_ordered`); threshold (n_rows,) finite, in the units of the draws, compared with strict >;
+  observed_longest / observed_spells / observed_onset_step (G,) the observed values, NaN where a group is not to be
+  scored.  -> dict of numpy arrays, for name in 'longest', 'spells', 'onset_step' (censored at the group's size when a
+  path never goes above):
+    '<name>_mean' (G,)  '<name>_quantiles' (len(quantiles), G)   numpy's default 'linear' rule
+    '<name>_crps' (G,)  '<name>_pit' (2, G)                      with observed_<name>, as `total_summaries` forms them
+  and
+    'onset_count' (n_rows,) int64     the paths in which the row is its group's first row above its threshold
+    'onset_probability' (n_rows,)     onset_count / num_samples
+    'no_episode_count' (G,) int64     the paths that never go above (longest == 0, counted on the device)
+    'no_episode' (G,)                 no_episode_count / num_samples = 1 - the group's sum of onset_probability
+  The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells, ValueError beyond.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  if num_samples > _native.SUMMARY_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the episodes are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
+                     'sample paths')
+  levels = [float(v) for v in quantiles]
+  if any(not 0.0 <= v <= 1.0 for v in levels):
+    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the matrices are held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  if threshold is None:
+    raise ValueError('threshold is required: one limit per row')
+  threshold = np.ascontiguousarray(threshold, dtype=np.float64)
+  if threshold.shape != (n_rows,):
+    raise ValueError(f'threshold must hold one limit per row ({n_rows},); got {threshold.shape}')
+  if not np.all(np.isfinite(threshold)):
+    raise ValueError('threshold must be finite')
+  observed = {}
+  for name, obs in zip(EPISODE_SERIES, (observed_longest, observed_spells, observed_onset_step)):
+    if obs is not None:
+      observed[name] = np.ascontiguousarray(obs, dtype=np.float64)
+      if observed[name].shape != (n_groups,):
+        raise ValueError(f'observed_{name} must hold one value per group ({n_groups},); got {observed[name].shape}')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
+  seed64 = _native.seed_to_u64(seed)
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    ep = eng.predictive_group_episodes(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
+                                       num_samples, seed64, threshold.astype(np.float32), **kw)
+    out = {'onset_count': ep['onset_count'].cpu().numpy().astype(np.int64),
+           'no_episode_count': (ep['longest'] == 0).sum(dim=0).cpu().numpy().astype(np.int64)}
+    out['onset_probability'] = out['onset_count'].astype(np.float64) / num_samples
+    out['no_episode'] = out['no_episode_count'].astype(np.float64) / num_samples
+    for name in EPISODE_SERIES:
+      y = torch.from_numpy(observed[name]).to(eng.device) if name in observed else None
+      for k, v in eng.sample_summaries(ep[name], y, levels).items():
+        out[f'{name}_{k}'] = v.cpu().numpy()
     return out
   finally:
     eng.close()

@@ -183,6 +183,13 @@ def group_rows(table, group_by):
   """Rows of `table` grouped by one column or a list of columns -> (keys, seg_offsets, seg_rows): `keys` the sorted
   pandas Index (a MultiIndex for several columns) of the groups that occur, and the rows sorted by group as CSR
   (`inference.csr_from_codes`): group keys[g] owns seg_rows[seg_offsets[g]:seg_offsets[g + 1]]."""
+  keys, codes = _group_codes(table, group_by)
+  seg_offsets, seg_rows = inference.csr_from_codes(codes, len(keys))
+  return keys, seg_offsets, seg_rows
+
+
+def _group_codes(table, group_by):
+  """-> (keys, codes): the sorted Index of the groups that occur and every row's group as a position in it."""
   cols = [group_by] if isinstance(group_by, str) or not isinstance(group_by, (list, tuple)) else list(group_by)
   missing = [c for c in cols if c not in table.columns]
   if not cols or missing:
@@ -194,7 +201,19 @@ def group_rows(table, group_by):
   keys = keys.set_names(cols)
   if (codes < 0).any():
     raise ValueError('group_by columns hold missing values')
-  seg_offsets, seg_rows = inference.csr_from_codes(codes.astype(np.int64), len(keys))
+  return keys, codes.astype(np.int64)
+
+
+def group_rows_ordered(table, group_by, order_by):
+  """`group_rows` with the rows of every group in the order of the column `order_by`: ascending, rows with equal
+  values in table order (`inference.csr_ordered`).  The layout in which position order inside a group is time."""
+  keys, codes = _group_codes(table, group_by)
+  if not isinstance(order_by, str) or order_by not in table.columns:
+    raise ValueError(f'order_by: {order_by!r} is not among the columns of the table')
+  rank, _ = pd.factorize(table[order_by], sort=True)          # any sortable column -> its rank
+  if (rank < 0).any():
+    raise ValueError(f'order_by: the column {order_by!r} holds missing values')
+  seg_offsets, seg_rows = inference.csr_ordered(codes, len(keys), rank.astype(np.int64))
   return keys, seg_offsets, seg_rows
 
 
@@ -238,6 +257,40 @@ def group_target_extremes(target, seg_offsets, seg_rows, threshold=None):
       above = (sorted_target > np.asarray(threshold, dtype=np.float64)[order]).astype(np.float64)
       count[full] = np.where(seen, np.add.reduceat(above, starts[full]), np.nan)
   return peak, peak_row, count
+
+
+def group_target_episodes(target, seg_offsets, seg_rows, threshold):
+  """Observed spells: per group of a CSR layout whose positions are in time order (`group_rows_ordered`), with
+  above = target > threshold (both (R,)) read along the group's positions -> dict of (G,) arrays:
+    'longest' float64      length of the longest run of consecutive rows above, 0 if none
+    'longest_row' int64    the table row at which it starts (the earliest of equally long runs), -1 if none
+    'spells' float64       the number of maximal runs
+    'onset_step' float64   the rows before the first one above; the group's size if none (censored, as the forecast is)
+    'first_row', 'last_row' int64   the first / last table row above, -1 if none
+  A group with a NaN target among its rows (and an empty one, which `group_rows` never makes) gives NaN in the float
+  columns and -1 in the row columns: it is not scored."""
+  target = np.asarray(target, dtype=np.float64)
+  order = np.asarray(seg_rows, dtype=np.int64)
+  offsets = np.asarray(seg_offsets, dtype=np.int64)
+  above = target[order] > np.asarray(threshold, dtype=np.float64)[order]
+  missing = np.isnan(target[order])
+  n_groups = len(offsets) - 1
+  out = {k: np.full(n_groups, np.nan) for k in ('longest', 'spells', 'onset_step')}
+  out.update({k: np.full(n_groups, -1, dtype=np.int64) for k in ('longest_row', 'first_row', 'last_row')})
+  for g in range(n_groups):
+    a, b = offsets[g], offsets[g + 1]
+    if a == b or missing[a:b].any():
+      continue
+    hit = np.flatnonzero(above[a:b])
+    out['longest'][g], out['spells'][g], out['onset_step'][g] = 0.0, 0.0, float(b - a)
+    if hit.size:
+      cut = np.flatnonzero(np.diff(hit) > 1)
+      starts, ends = hit[np.r_[0, cut + 1]], hit[np.r_[cut, hit.size - 1]]
+      lengths = ends - starts + 1
+      best = int(np.argmax(lengths))                           # the first of equally long runs
+      out['longest'][g], out['spells'][g], out['onset_step'][g] = float(lengths[best]), float(len(starts)), float(hit[0])
+      out['longest_row'][g], out['first_row'][g], out['last_row'][g] = order[a + starts[best]], order[a + hit[0]], order[a + hit[-1]]
+  return out
 
 
 # ---------------------------------------------------------------------------
@@ -685,6 +738,100 @@ class BayesianNeuralFieldEstimator:
       brier = (res['exceed_any'] - hit) ** 2
       res.update(observed_count=obs_count, count_crps=out['count_crps'], count_pit=out['count_pit'], brier=brier,
                  mean_count_crps=mean(out['count_crps']), mean_brier=mean(brier))
+    return res
+
+  def _episode_summaries(self, what, table, group_by, threshold, order_by, quantiles, num_samples, seed, target=None,
+                         weights=None):
+    if int(num_samples) < 1:
+      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
+    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{what}: num_samples={num_samples}: the episodes are summarised from at most '
+                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    if threshold is None:
+      raise ValueError(f'{what}: threshold is required: a number or one number per row of the table')
+    try:
+      thr = np.asarray(threshold, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'{what}: threshold must be a number or one number per row of the table') from e
+    if thr.ndim == 0:
+      thr = np.full(len(table), float(thr))
+    if thr.shape != (len(table),):
+      raise ValueError(f'{what}: threshold must be a scalar or hold one limit per row ({len(table)},); got {thr.shape}')
+    if not np.all(np.isfinite(thr)):
+      raise ValueError(f'{what}: threshold must be finite')
+    thr = thr.astype(np.float32).astype(np.float64)            # the draws are float32: compared at that precision
+    kw = self._weights_kw(weights)
+    keys, seg_offsets, seg_rows = group_rows_ordered(
+        table, group_by, self.data_handler._time_column if order_by is None else order_by)
+    n_groups = len(keys)
+    if int(num_samples) * n_groups > inference._TOTALS_MAX_CELLS:
+      raise ValueError(f'{what}: {num_samples} sample paths x {n_groups} groups: the matrices are held whole on the '
+                       f'device, at most {inference._TOTALS_MAX_CELLS} cells')
+    observed = None if target is None else group_target_episodes(target, seg_offsets, seg_rows, thr)
+    rows = self.data_handler.get_test(table)
+    obs_kw = {} if observed is None else {f'observed_{k}': observed[k] for k in inference.EPISODE_SERIES}
+    out = inference.episode_summaries(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), threshold=thr, quantiles=tuple(quantiles),
+        compute_dtype=self.compute_dtype, **obs_kw, **kw)
+    res = {'keys': keys, 'onset_probability': out['onset_probability'], 'no_episode': out['no_episode']}
+    for name in inference.EPISODE_SERIES:
+      res[f'{name}_mean'], res[f'{name}_quantiles'] = out[f'{name}_mean'], out[f'{name}_quantiles']
+    return res, out, observed
+
+  def predict_episodes(self, table, group_by, threshold, order_by=None, quantiles=(0.5,), num_samples=1000, seed=0,
+                       weights=None):
+    """Spells above a threshold in the sample paths of `predict_samples(table, num_samples, seed)`: when a group's
+    series first goes above its limit, how long it stays there and whether it is one wave or several, formed and
+    summarised on the GPU (neither the draws nor the (num_samples, G) matrices leave the device).  These depend on the
+    ORDER of a group's rows: `order_by=None` orders them by the time column (feature_cols[0]), a column name by that
+    column; ties keep table order.  threshold: a scalar or one finite limit per row, in the units of the target column,
+    compared with strict > at float32 precision (the precision of the draws).  -> dict:
+      'keys'                     the groups, as in `predict_samples`
+      'longest_mean' (G,)  'longest_quantiles' (len(quantiles), G)   the longest run of consecutive rows above
+      'spells_mean', 'spells_quantiles'                              the number of separate runs
+      'onset_step_mean', 'onset_step_quantiles'                      the rows before the first one above; a path that
+                                 never goes above counts the group's size (censored at the horizon)
+      'onset_probability' (len(table),)   the share of the paths in which the row is its group's first row above
+      'no_episode' (G,)          the share of the paths that never go above: 1 - the group's sum of 'onset_probability'
+    num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    if self.params_ is None:
+      raise ValueError('predict_episodes before fit')
+    res, _, _ = self._episode_summaries('predict_episodes', table, group_by, threshold, order_by, quantiles, num_samples,
+                                        seed, weights=weights)
+    return res
+
+  def score_episodes(self, table, group_by, threshold, order_by=None, quantiles=(0.025, 0.5, 0.975), num_samples=1000,
+                     seed=0, weights=None):
+    """The forecast of `predict_episodes` scored against the spells observed in `table[target_col]`, on the GPU.  -> the
+    dict of `predict_episodes` plus, for name in 'longest', 'spells', 'onset_step':
+      'observed_<name>' (G,)     `group_target_episodes` on the target (onset_step censored as the forecast is); NaN when
+                                 any row of the group has a NaN target: such a group is not scored
+      '<name>_crps' (G,)  '<name>_pit' (2, G)   ensemble CRPS and the share of the sampled values <= and < the observed
+                                 one; NaN where not scored
+      'mean_<name>_crps'         mean over the scored groups
+    and
+      'observed_onset_row' (G,)  the first table row above its threshold, -1 if none (or not scored)
+      'onset_row_probability' (G,)   the forecast probability ('onset_probability') of the observed onset row, or
+                                 'no_episode' when nothing was observed above; NaN where not scored
+      'n'                        number of groups scored       'mean_onset_row_probability'
+    The target checks are those of `score_totals`."""
+    if self.params_ is None:
+      raise ValueError('score_episodes before fit')
+    y = self._targets('score_episodes', table)
+    res, out, observed = self._episode_summaries(
+        'score_episodes', table, group_by, threshold, order_by, quantiles, num_samples, seed, target=y, weights=weights)
+    scored = ~np.isnan(observed['longest'])
+    mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
+    first = observed['first_row']
+    prob = np.where(first >= 0, res['onset_probability'][np.maximum(first, 0)], res['no_episode'])
+    prob = np.where(scored, prob, np.nan)
+    res.update(observed_onset_row=first, onset_row_probability=prob, n=int(scored.sum()),
+               mean_onset_row_probability=mean(prob))
+    for name in inference.EPISODE_SERIES:
+      res[f'observed_{name}'] = observed[name]
+      res[f'{name}_crps'], res[f'{name}_pit'] = out[f'{name}_crps'], out[f'{name}_pit']
+      res[f'mean_{name}_crps'] = mean(out[f'{name}_crps'])
     return res
 
   def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=None, p=0.5,

@@ -356,6 +356,42 @@ int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* 
                                   const float* threshold, void* work, size_t work_bytes, double* out_max,
                                   int32_t* out_argmax, double* out_count, uint32_t* peak_count, uint32_t* exceed_count);
 
+/* SPELLS above a threshold in the same sample paths, per group of rows, without materialising the draws (the reference
+ * has no counterpart: it would loop over `.sample()` on the host).  The value at (path s, row r) is the f32 that
+ * bnf_predictive_samples writes for (seed, sample0 + s, row0 + r), bit for bit; loc, aux, seg_offsets, seg_rows, row0,
+ * sample0 and cum_weights (NULL = equal weights) as for bnf_predictive_group_extremes.  TIME is the order of the
+ * positions of seg_rows inside a group (sort the rows of a group by time: inference.csr_ordered).
+ *   threshold DEVICE (n_rows,) f32, required: a position EXCEEDS when its draw is strictly greater than threshold[row].
+ *     A NaN draw does not exceed but takes part: it breaks a spell and counts as a step.  An entry of seg_rows outside
+ *     [0, n_rows) takes no part: it neither breaks a spell nor counts as a step.
+ * Per (path s, group g), each skipped when its pointer is NULL except out_longest:
+ *   out_longest DEVICE (n_samples, n_groups) f64: length of the longest run of consecutive exceeding positions, 0 if none
+ *   out_longest_row DEVICE (n_samples, n_groups) int32: the TABLE ROW (an entry of seg_rows) at which that run starts;
+ *     among equally long runs the earliest wins; -1 if none
+ *   out_spells DEVICE (n_samples, n_groups) f64: the number of maximal runs
+ *   out_onset_step DEVICE (n_samples, n_groups) f64: the number of participating positions before the first exceeding
+ *     one; when the path never exceeds, the number of participating positions of the group (censored at the horizon,
+ *     never NaN: bnf_sample_summaries takes the matrix)
+ *   out_first_row, out_last_row DEVICE (n_samples, n_groups) int32: table row of the first / last exceeding position, -1
+ *     if none
+ *   onset_count DEVICE (n_rows,) uint32 or NULL, ZEROED BY THE CALLER, added to with integer atomics only:
+ *     onset_count[r] += the number of paths in which r is its group's first exceeding row
+ * A group without a participating position reports 0 / -1 / 0 / 0 / -1 / -1.
+ * The reduction joins pieces (len, lead, pre, suf, suf_pos, best, best_pos, runs, first, last) in position order with an
+ * associative, all-integer operator (bnf_episodes.h): the result does not depend on tile edges, the launch geometry or
+ * the number of passes, and two calls give the same bits.  No floating-point atomics.
+ *   work DEVICE, work_bytes: per-tile pieces, BNF_EPISODES_WORK_PER_TILE bytes x ceil(n_rows / BNF_GROUP_TILE) per sample
+ *     path; the samples are processed in as many passes as the buffer asks for (BNF_ERR_INVALID below one path's worth)
+ * BNF_ERR_INVALID also for a NULL threshold or out_longest and for n_members, n_rows, n_groups or n_samples < 1.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+#define BNF_EPISODES_WORK_PER_TILE 80
+int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
+                                  const float* threshold, void* work, size_t work_bytes, double* out_longest,
+                                  int32_t* out_longest_row, double* out_spells, double* out_onset_step,
+                                  int32_t* out_first_row, int32_t* out_last_row, uint32_t* onset_count);
+
 /* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
  * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
  * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
