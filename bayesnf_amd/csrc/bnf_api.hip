@@ -39,6 +39,7 @@
 #include "bnf_rps.h"
 #include "bnf_totals.h"
 #include "bnf_dependence.h"
+#include "bnf_ranking.h"
 #include "bnf_stacking.h"
 
 using namespace bnf;
@@ -2491,6 +2492,47 @@ int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, i
       hipLaunchKernelGGL(k_vario_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, nT * (nT + 1) / 2, y,
                          n_cols, score);
   }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- ranks of the columns within a sample path, rank probabilities (bnf_ranking.h) ------
+int bnf_sample_ranks(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
+                     double* out_rank, int32_t* out_above, int32_t* out_ties) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!x || n_samples < 1 || n_cols < 1) return fail(BNF_ERR_INVALID, "argument");
+  if (n_cols > BNF_RANK_MAX_COLS)
+    return fail(BNF_ERR_INVALID, "%lld columns: a path's values are sorted in LDS, at most %d", (long long)n_cols,
+                BNF_RANK_MAX_COLS);
+  if (!out_rank && !out_above && !out_ties) return fail(BNF_ERR_INVALID, "no output: rank, above and ties are all NULL");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  int P = 1;
+  while (P < n_cols) P <<= 1;
+  const int threads = std::min(1024, std::max(64, P / 2));          // a multiple of 64: P is a power of two
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_sample_ranks, (int)(sizeof(uint64_t) * kRankMaxCols), &attr_done);
+  hipLaunchKernelGGL(k_sample_ranks, dim3((unsigned)std::min<int64_t>(n_samples, 1 << 16)), dim3(threads),
+                     sizeof(uint64_t) * (size_t)P, h->stream, x, n_samples, (int32_t)n_cols, (int32_t)P, scale, out_rank,
+                     out_above, out_ties);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_rank_probabilities(bnf_handle* h, const int32_t* above, const int32_t* ties, int64_t n_samples, int64_t n_cols,
+                           int32_t top_k, double* out) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!above || !ties || !out || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  if (top_k < 1 || top_k > n_cols)
+    return fail(BNF_ERR_INVALID, "top_k = %d: 1..%lld, the number of columns", top_k, (long long)n_cols);
+  if ((int64_t)top_k * n_cols > BNF_RANK_MAX_CELLS)
+    return fail(BNF_ERR_INVALID, "top_k = %d x %lld columns: at most %d cells", top_k, (long long)n_cols,
+                BNF_RANK_MAX_CELLS);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_rank_probabilities, dim3(cdiv(n_cols, kRankSlab), cdiv(top_k, kRankKPerBlock)), dim3(256), 0,
+                     h->stream, above, ties, n_samples, n_cols, top_k, out);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -696,6 +696,56 @@ class Engine:
       out['variogram_score'] = float(score.cpu()[0])
     return out
 
+  def sample_ranks(self, x, scale=None) -> dict:
+    """How the columns of every joint path of x (S, G) f64 rank against each other (include/bnf.h bnf_sample_ranks), on
+    the values x / scale with scale (G,) an optional per-column divisor -> dict of (S, G) device tensors:
+      'above' int32   columns of the path with a larger value
+      'ties' int32    columns of the path with an equal value, the column itself included
+      'rank' f64      the mid-rank above + (ties + 1) / 2: rank 1 is the largest value, tied columns share their block
+    -0.0 ties with +0.0; NaNs tie with each other and rank below everything.  G > BNF_RANK_MAX_COLS is a ValueError.
+    G log^2 G per path.  Deterministic."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, G = x.shape
+    if S < 1 or G < 1:
+      raise ValueError(f'x must hold at least one path and one column; got {tuple(x.shape)}')
+    if G > _native.RANK_MAX_COLS:
+      raise ValueError(f'{G} columns: the values of a path are ranked in LDS, at most {_native.RANK_MAX_COLS}')
+    scale = None if scale is None else self._as_f64(scale, (G,), 'scale')
+    out = {'rank': torch.empty((S, G), dtype=torch.float64, device=self.device),
+           'above': torch.empty((S, G), dtype=torch.int32, device=self.device),
+           'ties': torch.empty((S, G), dtype=torch.int32, device=self.device)}
+    _native.check(self.lib.bnf_sample_ranks(self.handle, _ptr(x), S, G, _ptr(scale), _ptr(out['rank']),
+                                            _ptr(out['above']), _ptr(out['ties'])), 'bnf_sample_ranks')
+    torch.cuda.synchronize(self.device)     # device copies of `x` and `scale` made here are released on return
+    return out
+
+  def rank_probabilities(self, above, ties, top_k) -> torch.Tensor:
+    """P(column g takes rank slot k), k = 1 .. top_k, from the (S, G) int32 matrices `sample_ranks` returns (include/bnf.h
+    bnf_rank_probabilities) -> (top_k, G) f64 device tensor: (1 / S) sum_s [above < k <= above + ties] / ties, a tied block
+    handing each of its slots out in equal shares.  Every row sums to 1 over the columns.  1 <= top_k <= G and
+    top_k * G <= BNF_RANK_MAX_CELLS, ValueError otherwise.  Deterministic."""
+    if not (isinstance(above, torch.Tensor) and isinstance(ties, torch.Tensor)):
+      raise ValueError('above and ties must be the device tensors sample_ranks returns')
+    if above.dim() != 2 or above.shape != ties.shape or above.dtype != torch.int32 or ties.dtype != torch.int32:
+      raise ValueError(f'above and ties must be int32 of one shape (n_samples, n_cols); got {tuple(above.shape)} '
+                       f'{above.dtype} and {tuple(ties.shape)} {ties.dtype}')
+    above, ties = above.to(self.device).contiguous(), ties.to(self.device).contiguous()
+    S, G = above.shape
+    if S < 1 or G < 1:
+      raise ValueError(f'above must hold at least one path and one column; got {tuple(above.shape)}')
+    top_k = int(top_k)
+    if not 1 <= top_k <= G:
+      raise ValueError(f'top_k={top_k}: 1..{G}, the number of columns')
+    if top_k * G > _native.RANK_MAX_CELLS:
+      raise ValueError(f'top_k={top_k} x {G} columns: at most {_native.RANK_MAX_CELLS} cells')
+    out = torch.empty((top_k, G), dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_rank_probabilities(self.handle, _ptr(above), _ptr(ties), S, G, top_k, _ptr(out)),
+                  'bnf_rank_probabilities')
+    torch.cuda.synchronize(self.device)     # device copies made here are released on return
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

@@ -551,6 +551,121 @@ def dependence_summaries(features, observation_model, params, model_args, num_sa
     eng.close()
 
 
+def ranking_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                      observed=None, scale=None, top_k=1, quantiles=(), compute_dtype=None, weights=None):
+  """How the group totals of the joint sample paths rank against each other within a path, formed and scored on the GPU:
+  the (num_samples, G) matrix `sample_predictive(..., groups=groups)` would return stays on the device (include/bnf.h
+  bnf_predictive_group_sums), every path is ranked there (bnf_sample_ranks: rank 1 is the largest total, tied groups
+  share their block of ranks), and only the results come back.  groups = (seg_offsets, seg_rows) as `csr_from_codes`
+  builds them; scale (G,) finite and > 0 divides the totals before they are ranked (a population: rank per capita);
+  observed (G,) the observed totals, NaN where a group is not to be scored.
+  -> dict of numpy arrays, float64 unless noted:
+    'rank_mean' (G,)   'rank_quantiles' (len(quantiles), G)   of the mid-rank over the paths (bnf_sample_summaries)
+    'rank_probability' (top_k, G)                             P(the group takes rank slot k), ties sharing
+                                                              (bnf_rank_probabilities); every row sums to 1
+  and with `observed`:
+    'observed_rank' (G,)  'observed_above' (G,) int64  'observed_ties' (G,) int64
+                                      bnf_sample_ranks on the observed totals as one path; NaN / -1 / -1 where not scored
+    'rank_crps' (G,)  'rank_pit' (2, G)   the ensemble CRPS and PIT of the mid-rank against the observed one
+    'scored_rank_mean', 'scored_rank_quantiles', 'scored_rank_probability'   the three forecast outputs of the ranking
+                                      AMONG THE SCORED GROUPS (NaN in the other columns; rows k > their number are 0)
+  When `observed` holds NaN the scored forecast is not the plain one: the scored columns are selected on the device and
+  ranked again among themselves, so that forecast and observed ranks mean the same thing; the plain outputs rank all groups.
+  num_samples <= 16,384 (the summaries' cap), num_samples * G <= 2^28 cells, G <= 16,384, 1 <= top_k <= G and
+  top_k * G <= 2^24; ValueError beyond, before any GPU work.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  if num_samples > _native.SUMMARY_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the ranks are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
+                     'sample paths')
+  levels = [float(v) for v in quantiles]
+  if any(not 0.0 <= v <= 1.0 for v in levels):
+    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  if n_groups > _native.RANK_MAX_COLS:
+    raise ValueError(f'{n_groups} groups: the totals of a path are ranked in LDS, at most {_native.RANK_MAX_COLS}')
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+  try:
+    top_k = int(top_k)
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'top_k must be an integer in 1..{n_groups}') from e
+  if not 1 <= top_k <= n_groups:
+    raise ValueError(f'top_k={top_k}: 1..{n_groups}, the number of groups')
+  if top_k * n_groups > _native.RANK_MAX_CELLS:
+    raise ValueError(f'top_k={top_k} x {n_groups} groups: at most {_native.RANK_MAX_CELLS} rank probabilities')
+  if observed is not None:
+    observed = np.ascontiguousarray(observed, dtype=np.float64)
+    if observed.shape != (n_groups,):
+      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  if scale is not None:
+    try:
+      scale = np.ascontiguousarray(scale, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'scale must be an array of numbers of shape ({n_groups},)') from e
+    if scale.shape != (n_groups,):
+      raise ValueError(f'scale must hold one divisor per group ({n_groups},); got {scale.shape}')
+    if not (np.all(np.isfinite(scale)) and np.all(scale > 0)):
+      raise ValueError('scale must be finite and > 0')
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
+  seed64 = _native.seed_to_u64(seed)
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  net, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
+                                       num_samples, seed64, **kw)
+    sc = None if scale is None else torch.from_numpy(scale).to(eng.device)
+
+    def forecast(x, s, y_rank, k):
+      r = eng.sample_ranks(x, s)
+      summ = eng.sample_summaries(r['rank'], y_rank, levels)
+      return summ, eng.rank_probabilities(r['above'], r['ties'], k)
+
+    host = lambda t: t.cpu().numpy()
+    scored = None if observed is None else ~np.isnan(observed)
+    out = {}
+    if scored is None or not scored.all():              # the plain forecast: all groups
+      summ, prob = forecast(totals, sc, None, top_k)
+      out.update(rank_mean=host(summ['mean']), rank_quantiles=host(summ['quantiles']), rank_probability=host(prob))
+    if scored is not None:
+      n = int(scored.sum())
+      sub = {'rank_mean': np.full(n_groups, np.nan), 'rank_quantiles': np.full((len(levels), n_groups), np.nan),
+             'rank_probability': np.full((top_k, n_groups), np.nan), 'rank_crps': np.full(n_groups, np.nan),
+             'rank_pit': np.full((2, n_groups), np.nan)}
+      obs_rank, obs_above, obs_ties = np.full(n_groups, np.nan), np.full(n_groups, -1), np.full(n_groups, -1)
+      if n:
+        whole = n == n_groups
+        idx = None if whole else torch.from_numpy(np.flatnonzero(scored)).to(eng.device)
+        x = totals if whole else totals.index_select(1, idx)
+        s = sc if whole or sc is None else sc.index_select(0, idx)
+        y = torch.from_numpy(observed).to(eng.device)
+        y = y if whole else y.index_select(0, idx)
+        o = eng.sample_ranks(y.reshape(1, n), s)        # the observed ranks: the same call on one path
+        k = min(top_k, n)
+        summ, prob = forecast(x, s, o['rank'].reshape(n), k)
+        sub['rank_mean'][scored], sub['rank_quantiles'][:, scored] = host(summ['mean']), host(summ['quantiles'])
+        sub['rank_crps'][scored], sub['rank_pit'][:, scored] = host(summ['crps']), host(summ['pit'])
+        sub['rank_probability'][:k, scored] = host(prob)
+        sub['rank_probability'][k:, scored] = 0.0       # among n groups no rank slot beyond n is ever taken
+        obs_rank[scored] = host(o['rank'])[0]
+        obs_above[scored], obs_ties[scored] = host(o['above'])[0], host(o['ties'])[0]
+      if scored.all():
+        out.update({key: sub[key] for key in ('rank_mean', 'rank_quantiles', 'rank_probability')})
+      out.update(observed_rank=obs_rank, observed_above=obs_above, observed_ties=obs_ties, rank_crps=sub['rank_crps'],
+                 rank_pit=sub['rank_pit'], scored_rank_mean=sub['rank_mean'], scored_rank_quantiles=sub['rank_quantiles'],
+                 scored_rank_probability=sub['rank_probability'])
+    return out
+  finally:
+    eng.close()
+
+
 def extreme_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
                       threshold=None, observed_max=None, observed_count=None, quantiles=(), compute_dtype=None,
                       weights=None):

@@ -231,6 +231,31 @@ def group_target_sums(target, seg_offsets, seg_rows):
   return out
 
 
+def group_target_ranks(observed, scale=None):
+  """Observed ranks: the groups ranked by their observed totals `observed` (G,), divided by `scale` (G,) when given,
+  with the tie rule of the forecast (include/bnf.h bnf_sample_ranks) -> (rank (G,) float64, above (G,) int64, ties (G,)
+  int64): above the groups with a larger value, ties those with an equal one (the group itself included), rank the
+  mid-rank above + (ties + 1) / 2, so rank 1 is the largest and tied groups share their block of ranks.  A group with a
+  NaN total gives NaN / -1 / -1 and takes no part in the ranks of the others."""
+  v = np.asarray(observed, dtype=np.float64)
+  if v.ndim != 1:
+    raise ValueError(f'observed must be (G,); got {v.shape}')
+  if scale is not None:
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.shape != v.shape:
+      raise ValueError(f'scale must hold one divisor per group {v.shape}; got {scale.shape}')
+    v = v / scale
+  seen = ~np.isnan(v)
+  rank, above, ties = np.full(v.shape, np.nan), np.full(v.shape, -1), np.full(v.shape, -1)
+  w = v[seen]
+  ordered = np.sort(w)
+  hi = np.searchsorted(ordered, w, side='right')
+  ties[seen] = hi - np.searchsorted(ordered, w, side='left')
+  above[seen] = w.size - hi
+  rank[seen] = above[seen] + 0.5 * (ties[seen] + 1)
+  return rank, above, ties
+
+
 def group_target_extremes(target, seg_offsets, seg_rows, threshold=None):
   """Observed peaks: per group of the CSR layout `group_rows` returns, the largest `target` (R,) over the group's rows,
   the lowest table row at which it is reached and, with `threshold` (R,), the number of rows whose target is > their
@@ -517,7 +542,7 @@ class BayesianNeuralFieldEstimator:
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
-    `predict_dependence` and `score_dependence` (weights=...) and scored on
+    `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking` (weights=...) and scored on
     another table by `weighted_log_density`; they are taken by the marginal forecast as well: `predict` and `score`
     (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.  `fit` is unchanged."""
     if self.params_ is None:
@@ -913,6 +938,119 @@ class BayesianNeuralFieldEstimator:
       w = np.asarray(pair_weights, dtype=np.float64)[np.ix_(scored, scored)]
       total = float(np.sum(np.triu(w, 1), dtype=np.float64))
     res['mean_variogram_score'] = res['variogram_score'] / total if res['n_pairs'] > 0 and total > 0 else float('nan')
+    return res
+
+  @staticmethod
+  def _per_group(what, table, per, seg_offsets, seg_rows):
+    """The divisor of every group from `per`: None, a column of `table` or one value per table row; constant within every
+    group, finite and > 0 -> (G,) float64 or None."""
+    if per is None:
+      return None
+    if isinstance(per, str):
+      if per not in table.columns:
+        raise ValueError(f'{what}: per: {per!r} is not among the columns of the table')
+      per = table[per].values
+    try:
+      v = np.asarray(per, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'{what}: per must be a column of the table or one number per row') from e
+    if v.shape != (len(table),):
+      raise ValueError(f'{what}: per must hold one value per row ({len(table)},); got {v.shape}')
+    if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+      raise ValueError(f'{what}: per must be finite and > 0')
+    ordered = v[np.asarray(seg_rows, dtype=np.int64)]
+    starts = np.asarray(seg_offsets[:-1], dtype=np.int64)
+    lo, hi = np.minimum.reduceat(ordered, starts), np.maximum.reduceat(ordered, starts)
+    if np.any(lo != hi):
+      raise ValueError(f'{what}: per must be constant within every group')
+    return lo
+
+  def _ranking_summaries(self, what, table, group_by, top_k, per, quantiles, num_samples, seed, weights, target=None):
+    if int(num_samples) < 1:
+      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
+    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{what}: num_samples={num_samples}: the ranks are summarised from at most '
+                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    kw = self._weights_kw(weights)
+    keys, seg_offsets, seg_rows = group_rows(table, group_by)
+    scale = self._per_group(what, table, per, seg_offsets, seg_rows)
+    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
+    rows = self.data_handler.get_test(table)
+    out = inference.ranking_summaries(
+        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, scale=scale, top_k=top_k,
+        quantiles=tuple(quantiles), compute_dtype=self.compute_dtype, **kw)
+    return out, keys, observed
+
+  @staticmethod
+  def _ranking_result(keys, mean, quant, prob):
+    lead = prob[0]
+    best = None if np.all(np.isnan(lead)) else keys[int(np.nanargmax(lead))]
+    return {'keys': keys, 'rank_mean': mean, 'rank_quantiles': quant, 'rank_probability': prob,
+            'top_probability': np.cumsum(prob, axis=0), 'most_likely_top': best}
+
+  def predict_ranking(self, table, group_by, top_k=3, per=None, quantiles=(0.5,), num_samples=1000, seed=0, weights=None):
+    """How the groups rank against each other by their totals in `predict_samples(table, num_samples, seed,
+    group_by=group_by)` -- "which places are among the three worst hit" -- formed on the GPU: every path is ranked on the
+    device and the (num_samples, G) matrix of totals never leaves it.  One member drives all rows of a path, so the totals
+    rise and fall together: the rank of a group is a property of the whole vector and of no marginal.  Rank 1 is the
+    largest total; groups whose totals tie in a path share their block of ranks equally (totals of counts tie often; they
+    are never told apart by their position).  -> dict:
+      'keys'                       the groups, as in `predict_samples`
+      'rank_mean' (G,)             'rank_quantiles' (len(quantiles), G)   of the mid-rank over the paths
+      'rank_probability' (top_k, G)   P(the group takes rank k), k = 1 .. top_k; every row sums to 1
+      'top_probability' (top_k, G) its running sum over k: P(the group is among the k largest), ties sharing
+      'most_likely_top'            the key of the group with the largest rank_probability[0]
+    per: None, or a column of `table` (or one value per row) that is constant within every group, finite and > 0, such as
+    a population: the groups are then ranked by total / per.  At most 16,384 groups, num_samples <= 16,384,
+    num_samples * G <= 2^28, 1 <= top_k <= G and top_k * G <= 2^24.  weights: member weights of the sample paths as in
+    `predict_samples`; None: equal weights."""
+    if self.params_ is None:
+      raise ValueError('predict_ranking before fit')
+    out, keys, _ = self._ranking_summaries('predict_ranking', table, group_by, top_k, per, quantiles, num_samples, seed,
+                                           weights)
+    return self._ranking_result(keys, out['rank_mean'], out['rank_quantiles'], out['rank_probability'])
+
+  def score_ranking(self, table, group_by, top_k=3, per=None, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0,
+                    weights=None):
+    """The forecast ranking of the groups scored against the ranking of the totals observed in `table[target_col]`, on
+    the GPU.  A group with a NaN target among its rows is not scored, and the scored forecast is the ranking AMONG THE
+    SCORED GROUPS (they are ranked again without the others, so that forecast and observed ranks mean the same thing).
+    -> the dict of `predict_ranking` among the scored groups, NaN in the columns of the others (rows k > n of
+    'rank_probability' are 0: no such rank is taken), plus
+      'observed' (G,)          sum of the target over the group's rows; NaN when any row of the group has a NaN target
+      'observed_rank' (G,)     the mid-rank of the observed total (divided by `per`) among the scored groups
+      'rank_crps' (G,)  'rank_pit' (2, G)   ensemble CRPS and PIT of the mid-rank over the paths against the observed one
+      'observed_top' (top_k, G)   the share of the group in the observed top k: clip((k - above) / ties, 0, 1) of the
+                               observed ranks -- 1 or 0 without ties
+      'top_brier' (top_k,)     mean over the scored groups of (top_probability - observed_top)^2
+      'observed_rank_probability' (G,)   the forecast probability of the observed rank block: the sum of 'rank_probability'
+                               over the ranks above + 1 .. above + ties that are <= top_k; NaN when the block lies wholly
+                               beyond top_k
+      'n'                      groups scored          'mean_rank_crps'  mean of 'rank_crps' over them
+    The target checks are those of `score_totals`; the limits and `per`, `weights` those of `predict_ranking`."""
+    if self.params_ is None:
+      raise ValueError('score_ranking before fit')
+    y = self._targets('score_ranking', table)
+    out, keys, observed = self._ranking_summaries('score_ranking', table, group_by, top_k, per, quantiles, num_samples,
+                                                  seed, weights, target=y)
+    prob = out['scored_rank_probability']
+    res = self._ranking_result(keys, out['scored_rank_mean'], out['scored_rank_quantiles'], prob)
+    scored = ~np.isnan(observed)
+    n = int(scored.sum())
+    above, ties = out['observed_above'].astype(np.float64), out['observed_ties'].astype(np.float64)
+    k = np.arange(1, prob.shape[0] + 1, dtype=np.float64)[:, None]
+    observed_top = np.where(scored[None, :], np.clip((k - above[None, :]) / np.where(scored, ties, 1.0)[None, :], 0.0, 1.0),
+                            np.nan)
+    in_block = (k > above[None, :]) & (k <= (above + ties)[None, :])
+    block = np.sum(np.where(in_block, prob, 0.0), axis=0)
+    block[~scored | (above + 1 > prob.shape[0])] = np.nan
+    err = (res['top_probability'] - observed_top) ** 2
+    res.update(observed=observed, observed_rank=out['observed_rank'], rank_crps=out['rank_crps'], rank_pit=out['rank_pit'],
+               observed_top=observed_top,
+               top_brier=np.mean(err[:, scored], axis=1, dtype=np.float64) if n else np.full(prob.shape[0], np.nan),
+               observed_rank_probability=block, n=n,
+               mean_rank_crps=float(np.mean(out['rank_crps'][scored], dtype=np.float64)) if n else float('nan'))
     return res
 
   def likelihood_model(self, table):

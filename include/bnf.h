@@ -577,6 +577,39 @@ int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, i
                             const double* pair_w, double* mean, double* cov, double* vario, void* work, size_t work_bytes,
                             double* score);
 
+/* How the columns of the joint sample paths RANK against each other within a path -- "which groups are among the k
+ * largest" -- which no marginal shows.  x as for bnf_sample_summaries, S = n_samples, G = n_cols.
+ * bnf_sample_ranks: per path s the ranked values are v_sg = x_sg / scale_g, a plain IEEE f64 division, with
+ *   scale DEVICE (G,) f64 a per-column divisor (a population: rank per capita), or NULL: v = x.  Not validated (reading it
+ *     would cost a sync): a bad scale gives meaningless ranks, never an access outside x / scale.
+ *   out_above DEVICE (S, G) int32: #{h : v_sh > v_sg}
+ *   out_ties DEVICE (S, G) int32: #{h : v_sh == v_sg}, which counts g itself: >= 1
+ *   out_rank DEVICE (S, G) f64: the mid-rank above + (ties + 1) / 2, a multiple of 0.5 -- rank 1 is the LARGEST value; the
+ *     matrix bnf_sample_summaries takes (mean rank, rank quantiles, CRPS / PIT against the observed ranks)
+ * Tied columns share their block of ranks equally and are never told apart by their index (totals of counts tie all the
+ * time).  The comparison is a total order: -0.0 and +0.0 tie, +inf values tie, NaNs tie with each other, and a NaN ranks
+ * below everything, -inf included; so the integers depend on the path's values alone, and sum_g rank_sg = G (G + 1) / 2.
+ * Each output is skipped when NULL; all three NULL is BNF_ERR_INVALID.  One workgroup sorts the G keys of a path in LDS
+ * (8 bytes each, padded to a power of two: G <= BNF_RANK_MAX_COLS, BNF_ERR_INVALID beyond) and every column finds its block
+ * by two binary searches: G log^2 G per path.  n_samples < 1 and n_cols < 1 are BNF_ERR_INVALID; there is no cap on
+ * n_samples.  The observed ranks are this call on the observed totals as a 1 x G matrix.
+ * bnf_rank_probabilities: out DEVICE (top_k, G) f64,
+ *   out[k - 1][g] = (1 / S) sum_s [above_sg < k <= above_sg + ties_sg] / ties_sg,   k = 1 .. top_k:
+ * the probability that column g takes rank slot k, a tied block handing each of its slots out in equal shares.  Every row
+ * k <= G sums to 1 over the columns (a slot is handed out once per path); with top_k = G every column sums to 1.  Every
+ * cell is one sequential f64 sum over the paths in path order (which stream through LDS BNF_RANK_PATH_CHUNK at a time),
+ * then divided by (double)S: its bits depend on S and on that column's above / ties only.  1 <= top_k <= n_cols and
+ * top_k * n_cols <= BNF_RANK_MAX_CELLS, BNF_ERR_INVALID otherwise.  above / ties are not validated.
+ * Both: no floating-point atomics, two calls give the same bits; they run on the handle's stream, do not touch the
+ * training state, work on forward-only handles; the observation model of the handle plays no part. */
+#define BNF_RANK_MAX_COLS 16384          /* one path's values sorted in LDS */
+#define BNF_RANK_PATH_CHUNK 32           /* paths per LDS chunk of bnf_rank_probabilities */
+#define BNF_RANK_MAX_CELLS (1 << 24)     /* top_k * n_cols of bnf_rank_probabilities: 128 MiB */
+int bnf_sample_ranks(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
+                     double* out_rank, int32_t* out_above, int32_t* out_ties);
+int bnf_rank_probabilities(bnf_handle* h, const int32_t* above, const int32_t* ties, int64_t n_samples, int64_t n_cols,
+                           int32_t top_k, double* out);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
