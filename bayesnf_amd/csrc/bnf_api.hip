@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bnf.h"
@@ -1374,57 +1375,39 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
+// the observation model of the handle as a compile-time constant: f(tag) with decltype(tag)::value the BNF_OBS_* code
+template <typename F>
+static void with_obs(const bnf_handle* h, F&& f) {
+  switch (h->cfg.obs_model) {
+    case BNF_OBS_NORMAL: f(std::integral_constant<int, BNF_OBS_NORMAL>{}); break;
+    case BNF_OBS_NB: f(std::integral_constant<int, BNF_OBS_NB>{}); break;
+    default: f(std::integral_constant<int, BNF_OBS_ZINB>{}); break;
+  }
+}
+
+// the passes of a group reduction through its work buffer, `chunk` sample paths each (group_chunk): launch(obs, s0, n)
+// enqueues the n paths from s0 on, obs as in with_obs
+template <typename F>
+static void group_passes(const bnf_handle* h, int64_t n_samples, int64_t chunk, F&& launch) {
+  with_obs(h, [&](auto obs) {
+    for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) launch(obs, s0, std::min(chunk, n_samples - s0));
+  });
+}
+
+// the launch shape of the sample-path kernels: x = blocks of `per_block` rows (positions), y = the samples, strided; the
+// combine kernel of a group reduction (one wave per tile and sample) takes (grid.x, cdiv(S, 4))
+static dim3 pred_grid(int64_t R, int64_t per_block, int64_t S) {
+  const int64_t gx = cdiv(R, per_block);
+  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));
+  return dim3((unsigned)gx, (unsigned)gy);
+}
+
 // posterior-predictive sampling launches (bnf_sampling.h), one instantiation per observation model
 template <int OBS>
 static void launch_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, int64_t S,
                                       uint64_t seed, int64_t row0, int64_t sample0, const double* cum, float* out) {
-  const int64_t gx = cdiv(R, 256 * kPredRowsPerThread);
-  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));
-  hipLaunchKernelGGL((k_predictive_samples<OBS>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
-                     (int32_t)M, R, S, seed, row0, sample0, cum, out);
-}
-
-template <int OBS>
-static void launch_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
-                                         const int32_t* seg_offsets, const int32_t* seg_rows, int64_t G, int64_t S,
-                                         uint64_t seed, int64_t row0, int64_t sample0, const double* cum, double* partial,
-                                         double* out) {
-  const int64_t nt = cdiv(R, kPredTile);
-  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
-  hipLaunchKernelGGL((k_predictive_group_sums<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc, aux,
-                     (int32_t)M, R, seg_offsets, seg_rows, (int32_t)G, S, seed, row0, sample0, cum, partial, out);
-  hipLaunchKernelGGL(k_predictive_group_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
-                     seg_offsets, (int32_t)G, R, S, partial, out);
-}
-
-// group peaks and exceedances of the same paths (bnf_extremes.h): the launch shape of the group sums
-template <int OBS>
-static void launch_predictive_group_extremes(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
-                                             const int32_t* seg_offsets, int64_t G, int64_t S, uint64_t seed, int64_t row0,
-                                             int64_t sample0, const double* cum, const float* threshold, ExtPiece* partial,
-                                             const ExtOut& o, uint32_t* exceed_count) {
-  const int64_t nt = cdiv(R, kPredTile);
-  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
-  hipLaunchKernelGGL((k_predictive_group_extremes<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc,
-                     aux, (int32_t)M, R, seg_offsets, o.seg_rows, (int32_t)G, S, seed, row0, sample0, cum, threshold,
-                     partial, o, exceed_count);
-  hipLaunchKernelGGL(k_predictive_group_extremes_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
-                     seg_offsets, (int32_t)G, R, S, partial, o);
-}
-
-// spells above a threshold in the same paths (bnf_episodes.h): the launch shape of the group sums
-template <int OBS>
-static void launch_predictive_group_episodes(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R,
-                                             const int32_t* seg_offsets, int64_t G, int64_t S, uint64_t seed, int64_t row0,
-                                             int64_t sample0, const double* cum, const float* threshold, EpPiece* partial,
-                                             const EpOut& o) {
-  const int64_t nt = cdiv(R, kPredTile);
-  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / nt));
-  hipLaunchKernelGGL((k_predictive_group_episodes<OBS>), dim3((unsigned)nt, (unsigned)gy), dim3(256), 0, h->stream, loc,
-                     aux, (int32_t)M, R, seg_offsets, o.seg_rows, (int32_t)G, S, seed, row0, sample0, cum, threshold,
-                     partial, o);
-  hipLaunchKernelGGL(k_predictive_group_episodes_combine, dim3((unsigned)nt, (unsigned)cdiv(S, 4)), dim3(256), 0, h->stream,
-                     seg_offsets, (int32_t)G, R, S, partial, o);
+  hipLaunchKernelGGL((k_predictive_samples<OBS>), pred_grid(R, 256 * kPredRowsPerThread, S), dim3(256), 0, h->stream, loc,
+                     aux, (int32_t)M, R, S, seed, row0, sample0, cum, out);
 }
 
 // held-out scoring launches (bnf_scoring.h), one instantiation per observation model and for the member weights wts
@@ -2073,11 +2056,9 @@ static int predictive_samples_impl(bnf_handle* h, const float* loc, const float*
   if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
   if (!out) return fail(BNF_ERR_INVALID, "argument");
   HIPCHK(hipSetDevice(h->cfg.device));
-  switch (h->cfg.obs_model) {
-    case BNF_OBS_NORMAL: launch_predictive_samples<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
-    case BNF_OBS_NB: launch_predictive_samples<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
-    default: launch_predictive_samples<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out); break;
-  }
+  with_obs(h, [&](auto obs) {
+    launch_predictive_samples<decltype(obs)::value>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2087,30 +2068,46 @@ int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, in
   return predictive_samples_impl(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, nullptr, out);
 }
 
+// what the three group reductions check alike: predictive_args, the CSR arrays, the work pointer and n_groups
+static int group_args(const bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                      const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                      int64_t row0, int64_t sample0, const void* work) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || !work || n_groups < 1 || n_groups > 0x7fffffffLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  return BNF_OK;
+}
+
+// *chunk = the sample paths one pass through the work buffer takes, at per_tile bytes per tile and path
+static int group_chunk(int64_t n_rows, int64_t n_samples, size_t per_tile, size_t work_bytes, int64_t* chunk) {
+  const size_t per_sample = (size_t)cdiv(n_rows, kPredTile) * per_tile;
+  *chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
+  if (*chunk < 1)
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
+                (long long)n_rows, per_sample);
+  return BNF_OK;
+}
+
 static int predictive_group_sums_impl(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
                                       const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
                                       int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, const double* cum,
                                       void* work, size_t work_bytes, double* out) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || !work || !out || n_groups < 1 || n_groups > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  const int64_t nt = cdiv(n_rows, kPredTile);
-  const size_t per_sample = (size_t)nt * 2 * sizeof(double);
-  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
-  if (chunk < 1)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
-                (long long)n_rows, per_sample);
+  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
+                                work)) return rc;
+  if (!out) return fail(BNF_ERR_INVALID, "argument");
+  int64_t chunk;
+  if (const int rc = group_chunk(n_rows, n_samples, 2 * sizeof(double), work_bytes, &chunk)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipMemsetAsync(out, 0, (size_t)n_samples * (size_t)n_groups * sizeof(double), h->stream));   // empty groups
-  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
-    const int64_t n = std::min(chunk, n_samples - s0);
-    double* o = out + s0 * n_groups;
-    switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_group_sums<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
-      case BNF_OBS_NB: launch_predictive_group_sums<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
-      default: launch_predictive_group_sums<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n, seed, row0, sample0 + s0, cum, (double*)work, o); break;
-    }
-  }
+  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
+    const dim3 grid = pred_grid(n_rows, kPredTile, n);
+    double* partial = (double*)work, *o = out + s0 * n_groups;
+    hipLaunchKernelGGL((k_predictive_group_sums<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
+                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
+                       cum, partial, o);
+    hipLaunchKernelGGL(k_predictive_group_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
+                       (int32_t)n_groups, n_rows, n, partial, o);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2152,33 +2149,29 @@ int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* 
                                   uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
                                   const float* threshold, void* work, size_t work_bytes, double* out_max,
                                   int32_t* out_argmax, double* out_count, uint32_t* peak_count, uint32_t* exceed_count) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || !work || !out_max || n_groups < 1 || n_groups > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
+  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
+                                work)) return rc;
+  if (!out_max) return fail(BNF_ERR_INVALID, "argument");
   if ((threshold == nullptr) != (out_count == nullptr) || (exceed_count && !threshold))
     return fail(BNF_ERR_INVALID, "out_count goes with threshold, and exceed_count needs one");
-  const int64_t nt = cdiv(n_rows, kPredTile);
-  const size_t per_sample = (size_t)nt * BNF_EXTREMES_WORK_PER_TILE;
-  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
-  if (chunk < 1)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
-                (long long)n_rows, per_sample);
+  int64_t chunk;
+  if (const int rc = group_chunk(n_rows, n_samples, BNF_EXTREMES_WORK_PER_TILE, work_bytes, &chunk)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   // groups without a row: max NaN (all bits set), argmax -1, count 0
   const size_t cells = (size_t)n_samples * (size_t)n_groups;
   HIPCHK(hipMemsetAsync(out_max, 0xff, cells * sizeof(double), h->stream));
   if (out_argmax) HIPCHK(hipMemsetAsync(out_argmax, 0xff, cells * sizeof(int32_t), h->stream));
   if (out_count) HIPCHK(hipMemsetAsync(out_count, 0, cells * sizeof(double), h->stream));
-  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
-    const int64_t n = std::min(chunk, n_samples - s0);
+  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
     const ExtOut o{seg_rows, out_max + s0 * n_groups, out_argmax ? out_argmax + s0 * n_groups : nullptr,
                    out_count ? out_count + s0 * n_groups : nullptr, peak_count};
-    switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_group_extremes<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
-      case BNF_OBS_NB: launch_predictive_group_extremes<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
-      default: launch_predictive_group_extremes<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (ExtPiece*)work, o, exceed_count); break;
-    }
-  }
+    const dim3 grid = pred_grid(n_rows, kPredTile, n);
+    hipLaunchKernelGGL((k_predictive_group_extremes<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
+                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
+                       cum_weights, threshold, (ExtPiece*)work, o, exceed_count);
+    hipLaunchKernelGGL(k_predictive_group_extremes_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
+                       (int32_t)n_groups, n_rows, n, (ExtPiece*)work, o);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2190,16 +2183,11 @@ int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* 
                                   const float* threshold, void* work, size_t work_bytes, double* out_longest,
                                   int32_t* out_longest_row, double* out_spells, double* out_onset_step,
                                   int32_t* out_first_row, int32_t* out_last_row, uint32_t* onset_count) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || !work || n_groups < 1 || n_groups > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
+  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
+                                work)) return rc;
   if (!threshold || !out_longest) return fail(BNF_ERR_INVALID, "threshold and out_longest are required");
-  const int64_t nt = cdiv(n_rows, kPredTile);
-  const size_t per_sample = (size_t)nt * BNF_EPISODES_WORK_PER_TILE;
-  const int64_t chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
-  if (chunk < 1)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
-                (long long)n_rows, per_sample);
+  int64_t chunk;
+  if (const int rc = group_chunk(n_rows, n_samples, BNF_EPISODES_WORK_PER_TILE, work_bytes, &chunk)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   // groups without a row: 0 / -1 / 0 / 0 / -1 / -1
   const size_t cells = (size_t)n_samples * (size_t)n_groups;
@@ -2209,18 +2197,18 @@ int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* 
   if (out_onset_step) HIPCHK(hipMemsetAsync(out_onset_step, 0, cells * sizeof(double), h->stream));
   if (out_first_row) HIPCHK(hipMemsetAsync(out_first_row, 0xff, cells * sizeof(int32_t), h->stream));
   if (out_last_row) HIPCHK(hipMemsetAsync(out_last_row, 0xff, cells * sizeof(int32_t), h->stream));
-  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) {
-    const int64_t n = std::min(chunk, n_samples - s0);
+  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
     const int64_t at = s0 * n_groups;
     const EpOut o{seg_rows, out_longest + at, out_longest_row ? out_longest_row + at : nullptr,
                   out_spells ? out_spells + at : nullptr, out_onset_step ? out_onset_step + at : nullptr,
                   out_first_row ? out_first_row + at : nullptr, out_last_row ? out_last_row + at : nullptr, onset_count};
-    switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_group_episodes<BNF_OBS_NORMAL>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
-      case BNF_OBS_NB: launch_predictive_group_episodes<BNF_OBS_NB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
-      default: launch_predictive_group_episodes<BNF_OBS_ZINB>(h, loc, aux, n_members, n_rows, seg_offsets, n_groups, n, seed, row0, sample0 + s0, cum_weights, threshold, (EpPiece*)work, o); break;
-    }
-  }
+    const dim3 grid = pred_grid(n_rows, kPredTile, n);
+    hipLaunchKernelGGL((k_predictive_group_episodes<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
+                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
+                       cum_weights, threshold, (EpPiece*)work, o);
+    hipLaunchKernelGGL(k_predictive_group_episodes_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
+                       (int32_t)n_groups, n_rows, n, (EpPiece*)work, o);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2246,19 +2234,15 @@ static int predictive_scores_impl(bnf_handle* h, const float* loc, const float* 
   HIPCHK(hipSetDevice(h->cfg.device));
   double* ll_partial = (double*)work;
   double* pair_partial = (double*)((char*)work + ll_bytes);
-  if (wts) {
-    switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-      case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-      default: launch_predictive_scores<BNF_OBS_ZINB, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-    }
-  } else {
-    switch (h->cfg.obs_model) {
-      case BNF_OBS_NORMAL: launch_predictive_scores<BNF_OBS_NORMAL, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-      case BNF_OBS_NB: launch_predictive_scores<BNF_OBS_NB, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-      default: launch_predictive_scores<BNF_OBS_ZINB, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots, member_ll, lpd, pit, crps); break;
-    }
-  }
+  with_obs(h, [&](auto obs) {
+    constexpr int OBS = decltype(obs)::value;
+    if (wts)
+      launch_predictive_scores<OBS, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots,
+                                          member_ll, lpd, pit, crps);
+    else
+      launch_predictive_scores<OBS, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots,
+                                           member_ll, lpd, pit, crps);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2278,11 +2262,10 @@ int bnf_member_log_density(bnf_handle* h, const float* loc, const float* aux, in
     return fail(BNF_ERR_INVALID, "argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   const dim3 grid(cdiv(n_rows, kStackTile), (unsigned)std::min<int64_t>(n_members, 65535));
-  switch (h->cfg.obs_model) {
-    case BNF_OBS_NORMAL: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_NORMAL>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
-    case BNF_OBS_NB: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_NB>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
-    default: hipLaunchKernelGGL((k_member_log_density<BNF_OBS_ZINB>), grid, dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, y, out); break;
-  }
+  with_obs(h, [&](auto obs) {
+    hipLaunchKernelGGL((k_member_log_density<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
+                       (int32_t)n_members, n_rows, y, out);
+  });
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

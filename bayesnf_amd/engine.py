@@ -53,6 +53,14 @@ def _ptr(t):
   return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def group_work_bytes(bytes_per_tile, R, n_samples):
+  """Size in bytes of the work buffer of a group reduction over R rows (include/bnf.h bnf_predictive_group_*): the
+  per-tile pieces of `bytes_per_tile` bytes per tile and path, for every path up to ~64 MB and for one path at least
+  (the library makes several passes beyond that)."""
+  per_path = bytes_per_tile * (-(-R // _native.GROUP_TILE))
+  return per_path * max(1, min(n_samples, (64 << 20) // per_path))
+
+
 class Engine:
   """One GPU's share of an ensemble: `members` networks trained side by side.
 
@@ -343,6 +351,27 @@ class Engine:
     f64 on the device, without materialising the draws.  The rows come sorted by group as CSR: seg_offsets (G + 1),
     seg_rows (R) int32 (`inference.csr_from_codes`).  Deterministic: the same call gives the same bits.
     cum_weights as for `predictive_samples` (bnf_predictive_group_sums_weighted); None: the equal-weight call."""
+    loc, aux, off, rows, M, R, G = self._group_inputs(loc, aux, seg_offsets, seg_rows)
+    n_samples = int(n_samples)
+    out = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+    work = self._group_work(16, R, n_samples)       # per-tile partial sums: two doubles per tile and path
+    if cum_weights is None:
+      _native.check(self.lib.bnf_predictive_group_sums(
+          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(work), C.c_size_t(work.numel()),
+          _ptr(out)), 'bnf_predictive_group_sums')
+    else:
+      cum = self._cum(cum_weights, M)
+      _native.check(self.lib.bnf_predictive_group_sums_weighted(
+          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(work),
+          C.c_size_t(work.numel()), _ptr(out)), 'bnf_predictive_group_sums_weighted')
+    torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
+    return out
+
+  def _group_inputs(self, loc, aux, seg_offsets, seg_rows):
+    """The inputs the group reductions share, normalised -> (loc (M, R) f32, aux f32, seg_offsets (G + 1,) int32,
+    seg_rows (R,) int32, M, R, G), all contiguous on the device."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
@@ -352,25 +381,19 @@ class Engine:
     G = off.numel() - 1
     if G < 1 or rows.numel() != R:
       raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
-    n_samples = int(n_samples)
-    out = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
-    # per-tile partial sums: 16 bytes per tile and path, at most ~64 MB (the library makes several passes beyond that)
-    per_path = 2 * (-(-R // _native.GROUP_TILE))
-    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // (8 * per_path))), dtype=torch.float64,
-                       device=self.device)
-    if cum_weights is None:
-      _native.check(self.lib.bnf_predictive_group_sums(
-          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
-          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(work), C.c_size_t(work.numel() * 8),
-          _ptr(out)), 'bnf_predictive_group_sums')
-    else:
-      cum = self._cum(cum_weights, M)
-      _native.check(self.lib.bnf_predictive_group_sums_weighted(
-          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
-          C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(work),
-          C.c_size_t(work.numel() * 8), _ptr(out)), 'bnf_predictive_group_sums_weighted')
-    torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
-    return out
+    return loc, aux, off, rows, M, R, G
+
+  def _row_threshold(self, threshold, R):
+    """threshold (R,) -> f32 device tensor, one limit per table row."""
+    thr = (threshold if isinstance(threshold, torch.Tensor)
+           else torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32))).to(self.device, dtype=torch.float32).contiguous()
+    if tuple(thr.shape) != (R,):
+      raise ValueError(f'threshold must hold one limit per row ({R},); got {tuple(thr.shape)}')
+    return thr
+
+  def _group_work(self, bytes_per_tile, R, n_samples):
+    """The work buffer of a group reduction (`group_work_bytes`); its numel() is the byte count the library takes."""
+    return torch.empty(group_work_bytes(bytes_per_tile, R, n_samples), dtype=torch.uint8, device=self.device)
 
   def predictive_group_extremes(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
                                 threshold=None, row0=0, sample0=0, cum_weights=None, per_row=True) -> dict:
@@ -383,21 +406,8 @@ class Engine:
       'peak_count' (R,) int32        per_row=True: the paths in which the row is its group's argmax
       'exceed_count' (R,) int32      per_row=True with `threshold`: the paths whose draw at the row is > its limit
     A group without rows gives max NaN, argmax -1, count 0.  Deterministic: the same call gives the same bits."""
-    loc = loc.contiguous().float()
-    aux = aux.contiguous().float()
-    M, R = loc.shape
-    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
-                        ).to(self.device, dtype=torch.int32).contiguous()
-    off, rows = as_i32(seg_offsets), as_i32(seg_rows)
-    G = off.numel() - 1
-    if G < 1 or rows.numel() != R:
-      raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
-    thr = None
-    if threshold is not None:
-      thr = (threshold if isinstance(threshold, torch.Tensor)
-             else torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32))).to(self.device, dtype=torch.float32).contiguous()
-      if tuple(thr.shape) != (R,):
-        raise ValueError(f'threshold must hold one limit per row ({R},); got {tuple(thr.shape)}')
+    loc, aux, off, rows, M, R, G = self._group_inputs(loc, aux, seg_offsets, seg_rows)
+    thr = None if threshold is None else self._row_threshold(threshold, R)
     n_samples = int(n_samples)
     out = {'max': torch.empty((n_samples, G), dtype=torch.float64, device=self.device),
            'argmax': torch.empty((n_samples, G), dtype=torch.int32, device=self.device)}
@@ -407,10 +417,7 @@ class Engine:
       out['peak_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
       if thr is not None:
         out['exceed_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
-    # per-tile pieces: BNF_EXTREMES_WORK_PER_TILE bytes per tile and path, at most ~64 MB (the library makes several
-    # passes beyond that)
-    per_path = _native.EXTREMES_WORK_PER_TILE * (-(-R // _native.GROUP_TILE))
-    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // per_path)), dtype=torch.uint8, device=self.device)
+    work = self._group_work(_native.EXTREMES_WORK_PER_TILE, R, n_samples)
     cum = self._cum(cum_weights, M)
     _native.check(self.lib.bnf_predictive_group_extremes(
         self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
@@ -435,21 +442,10 @@ class Engine:
       'first_row', 'last_row' (n_samples, G) int32   table row of the first / last exceeding position, -1 if none
       'onset_count' (R,) int32            per_row=True: the paths in which the row is its group's first exceeding row
     Deterministic: the same call gives the same bits."""
-    loc = loc.contiguous().float()
-    aux = aux.contiguous().float()
-    M, R = loc.shape
-    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
-                        ).to(self.device, dtype=torch.int32).contiguous()
-    off, rows = as_i32(seg_offsets), as_i32(seg_rows)
-    G = off.numel() - 1
-    if G < 1 or rows.numel() != R:
-      raise ValueError(f'seg_offsets needs >= 2 entries and seg_rows one entry per row ({R}); got {off.numel()}, {rows.numel()}')
+    loc, aux, off, rows, M, R, G = self._group_inputs(loc, aux, seg_offsets, seg_rows)
     if threshold is None:
       raise ValueError('threshold is required: one limit per row')
-    thr = (threshold if isinstance(threshold, torch.Tensor)
-           else torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32))).to(self.device, dtype=torch.float32).contiguous()
-    if tuple(thr.shape) != (R,):
-      raise ValueError(f'threshold must hold one limit per row ({R},); got {tuple(thr.shape)}')
+    thr = self._row_threshold(threshold, R)
     n_samples = int(n_samples)
     f64 = lambda: torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
     i32 = lambda: torch.empty((n_samples, G), dtype=torch.int32, device=self.device)
@@ -457,10 +453,7 @@ class Engine:
            'last_row': i32()}
     if per_row:                             # the library adds to it: zeroed here
       out['onset_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
-    # per-tile pieces: BNF_EPISODES_WORK_PER_TILE bytes per tile and path, at most ~64 MB (the library makes several
-    # passes beyond that)
-    per_path = _native.EPISODES_WORK_PER_TILE * (-(-R // _native.GROUP_TILE))
-    work = torch.empty(per_path * max(1, min(n_samples, (64 << 20) // per_path)), dtype=torch.uint8, device=self.device)
+    work = self._group_work(_native.EPISODES_WORK_PER_TILE, R, n_samples)
     cum = self._cum(cum_weights, M)
     _native.check(self.lib.bnf_predictive_group_episodes(
         self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,

@@ -15,6 +15,7 @@ per torchrun rank -- is `distributed.local_shards()`.
 
 from __future__ import annotations
 
+import contextlib
 import os
 import warnings
 from typing import Any
@@ -382,6 +383,69 @@ def mixture_weights(weights, params, ensemble_dims):
   return w, cum
 
 
+def _num_samples(num_samples, noun=None):
+  """The sample count as an int >= 1 and, for a forecast that goes through bnf_sample_summaries (`noun` says what is
+  summarised), at most its cap."""
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  if noun is not None and num_samples > _native.SUMMARY_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the {noun} are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
+                     'sample paths')
+  return num_samples
+
+
+def _quantile_levels(quantiles):
+  levels = [float(v) for v in quantiles]
+  if any(not 0.0 <= v <= 1.0 for v in levels):
+    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  return levels
+
+
+def _check_cells(num_samples, n_groups, held='totals matrix is'):
+  if num_samples * n_groups > _TOTALS_MAX_CELLS:
+    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the {held} held whole on the device, at '
+                     f'most {_TOTALS_MAX_CELLS} cells')
+
+
+def _per_group(name, noun, values, n_groups):
+  """An observed (G,) array as contiguous float64; None stays None."""
+  if values is None:
+    return None
+  values = np.ascontiguousarray(values, dtype=np.float64)
+  if values.shape != (n_groups,):
+    raise ValueError(f'{name} must hold one {noun} per group ({n_groups},); got {values.shape}')
+  return values
+
+
+def _row_threshold(threshold, n_rows):
+  """A (n_rows,) finite threshold as contiguous float64."""
+  threshold = np.ascontiguousarray(threshold, dtype=np.float64)
+  if threshold.shape != (n_rows,):
+    raise ValueError(f'threshold must hold one limit per row ({n_rows},); got {threshold.shape}')
+  if not np.all(np.isfinite(threshold)):
+    raise ValueError('threshold must be finite')
+  return threshold
+
+
+@contextlib.contextmanager
+def _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights, seed):
+  """What everything that draws sample paths starts from: the member weights checked, the seed, the forward pass of every
+  member -> (engine, loc (M, R), aux (M, 3), seed64, kw) with kw = {'cum_weights': ...} when weights are given, else {}.
+  The engine is closed on exit.  Every check of the caller comes before this: nothing above `_ensemble_forecast` touches
+  the GPU."""
+  _, cum = mixture_weights(weights, params, ensemble_dims)
+  kw = {} if cum is None else {'cum_weights': cum}
+  seed64 = _native.seed_to_u64(seed)
+  features = np.asarray(features, dtype=np.float64)
+  _, eng, _, loc_all, aux_all = _ensemble_forecast(
+      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
+  try:
+    yield eng, loc_all.reshape(-1, features.shape[0]), aux_all.reshape(-1, 3), seed64, kw
+  finally:
+    eng.close()
+
+
 def sample_predictive(features, observation_model, params, model_args, num_samples, seed, ensemble_dims,
                       groups=None, compute_dtype=None, weights=None):
   """Joint posterior-predictive draws on the GPU (include/bnf.h bnf_predictive_samples / bnf_predictive_group_sums;
@@ -395,30 +459,19 @@ def sample_predictive(features, observation_model, params, model_args, num_sampl
   values do not depend on the chunking (counter-based generator keyed by seed, path and global row).
   weights (shape of the ensemble dims, `mixture_weights`): path s draws its component with these probabilities instead
   of equal ones -- the weights `stack_members` returns.  None: nothing changes."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  loc = loc_all.reshape(-1, n_rows)
-  aux = aux_all.reshape(-1, 3)
-  try:
+  num_samples = _num_samples(num_samples)
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
     if groups is not None:
       seg_offsets, seg_rows = groups
       return eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw).cpu().numpy()
+    n_rows = loc.shape[1]
     out = np.empty((num_samples, n_rows), dtype=np.float32)
     chunk = max(1, _SAMPLE_CHUNK_CELLS // num_samples)
     for r0 in range(0, n_rows, chunk):
       r1 = min(n_rows, r0 + chunk)
       out[:, r0:r1] = eng.predictive_samples(loc[:, r0:r1], aux, num_samples, seed64, row0=r0, **kw).cpu().numpy()
     return out
-  finally:
-    eng.close()
 
 
 _TOTALS_MAX_CELLS = 1 << 28      # cells (sample x group, f64) of the totals matrix total_summaries holds on the device
@@ -439,42 +492,21 @@ def total_summaries(features, observation_model, params, model_args, num_samples
   The matrix is held whole (the energy score needs every column): num_samples <= 16,384 (BNF_SUMMARY_MAX_SAMPLES: a
   column is sorted in LDS) and num_samples * G <= 2^28 cells, ValueError beyond.
   weights: member weights of the sample paths as in `sample_predictive`; None: equal weights, nothing changes."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
-  if num_samples > _native.SUMMARY_MAX_SAMPLES:
-    raise ValueError(f'num_samples={num_samples}: the totals are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
-                     'sample paths')
-  levels = [float(v) for v in quantiles]
-  if any(not 0.0 <= v <= 1.0 for v in levels):
-    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  num_samples = _num_samples(num_samples, 'totals')
+  levels = _quantile_levels(quantiles)
   seg_offsets, seg_rows = groups
   n_groups = len(seg_offsets) - 1
-  if num_samples * n_groups > _TOTALS_MAX_CELLS:
-    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
-                     f'most {_TOTALS_MAX_CELLS} cells')
-  if observed is not None:
-    observed = np.ascontiguousarray(observed, dtype=np.float64)
-    if observed.shape != (n_groups,):
-      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  try:
-    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                       num_samples, seed64, **kw)
+  _check_cells(num_samples, n_groups)
+  observed = _per_group('observed', 'total', observed, n_groups)
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    totals = eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw)
     y = None if observed is None else torch.from_numpy(observed).to(eng.device)
     res = eng.sample_summaries(totals, y, levels)
     out = {k: v.cpu().numpy() for k, v in res.items()}
     if y is not None and energy:
       out['energy_score'] = eng.sample_energy_score(totals, y)
     return out
-  finally:
-    eng.close()
 
 
 VARIOGRAM_ORDERS = (0.5, 1.0, 2.0)      # the p the variogram is compiled for (include/bnf.h bnf_sample_pair_moments)
@@ -496,9 +528,7 @@ def dependence_summaries(features, observation_model, params, model_args, num_sa
   sample paths alone: nothing is sorted), and G <= 4,096 with `matrices` or `pair_weights`; ValueError beyond, before any
   GPU work.  num_samples G^2 / 2 pair terms.
   weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  num_samples = _num_samples(num_samples)
   try:
     p = float(p)
   except (TypeError, ValueError) as e:
@@ -507,16 +537,11 @@ def dependence_summaries(features, observation_model, params, model_args, num_sa
     raise ValueError(f'p={p!r}: the variogram is formed for p in {VARIOGRAM_ORDERS}')
   seg_offsets, seg_rows = groups
   n_groups = len(seg_offsets) - 1
-  if num_samples * n_groups > _TOTALS_MAX_CELLS:
-    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
-                     f'most {_TOTALS_MAX_CELLS} cells')
+  _check_cells(num_samples, n_groups)
   if (matrices or pair_weights is not None) and n_groups > _native.PAIR_MATRIX_MAX_COLS:
     raise ValueError(f'{n_groups} groups: a pair matrix (matrices=True, pair_weights) has at most '
                      f'{_native.PAIR_MATRIX_MAX_COLS} groups a side; matrices=False gives the variogram score alone')
-  if observed is not None:
-    observed = np.ascontiguousarray(observed, dtype=np.float64)
-    if observed.shape != (n_groups,):
-      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  observed = _per_group('observed', 'total', observed, n_groups)
   if pair_weights is not None:
     if observed is None:
       raise ValueError('pair_weights weight the variogram score: they need `observed`')
@@ -533,22 +558,13 @@ def dependence_summaries(features, observation_model, params, model_args, num_sa
       raise ValueError('pair_weights must be >= 0')
     if not np.array_equal(pair_weights, pair_weights.T):
       raise ValueError('pair_weights must be symmetric')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  try:
-    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                       num_samples, seed64, **kw)
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    totals = eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw)
     y = None if observed is None else torch.from_numpy(observed).to(eng.device)
     w = None if pair_weights is None else torch.from_numpy(pair_weights).to(eng.device)
     res = eng.sample_pair_moments(totals, p, y, w, matrices=bool(matrices))
     return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in res.items()}
-  finally:
-    eng.close()
 
 
 def ranking_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
@@ -574,22 +590,13 @@ def ranking_summaries(features, observation_model, params, model_args, num_sampl
   num_samples <= 16,384 (the summaries' cap), num_samples * G <= 2^28 cells, G <= 16,384, 1 <= top_k <= G and
   top_k * G <= 2^24; ValueError beyond, before any GPU work.
   weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
-  if num_samples > _native.SUMMARY_MAX_SAMPLES:
-    raise ValueError(f'num_samples={num_samples}: the ranks are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
-                     'sample paths')
-  levels = [float(v) for v in quantiles]
-  if any(not 0.0 <= v <= 1.0 for v in levels):
-    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  num_samples = _num_samples(num_samples, 'ranks')
+  levels = _quantile_levels(quantiles)
   seg_offsets, seg_rows = groups
   n_groups = len(seg_offsets) - 1
   if n_groups > _native.RANK_MAX_COLS:
     raise ValueError(f'{n_groups} groups: the totals of a path are ranked in LDS, at most {_native.RANK_MAX_COLS}')
-  if num_samples * n_groups > _TOTALS_MAX_CELLS:
-    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the totals matrix is held whole on the device, at '
-                     f'most {_TOTALS_MAX_CELLS} cells')
+  _check_cells(num_samples, n_groups)
   try:
     top_k = int(top_k)
   except (TypeError, ValueError) as e:
@@ -598,10 +605,7 @@ def ranking_summaries(features, observation_model, params, model_args, num_sampl
     raise ValueError(f'top_k={top_k}: 1..{n_groups}, the number of groups')
   if top_k * n_groups > _native.RANK_MAX_CELLS:
     raise ValueError(f'top_k={top_k} x {n_groups} groups: at most {_native.RANK_MAX_CELLS} rank probabilities')
-  if observed is not None:
-    observed = np.ascontiguousarray(observed, dtype=np.float64)
-    if observed.shape != (n_groups,):
-      raise ValueError(f'observed must hold one total per group ({n_groups},); got {observed.shape}')
+  observed = _per_group('observed', 'total', observed, n_groups)
   if scale is not None:
     try:
       scale = np.ascontiguousarray(scale, dtype=np.float64)
@@ -611,16 +615,9 @@ def ranking_summaries(features, observation_model, params, model_args, num_sampl
       raise ValueError(f'scale must hold one divisor per group ({n_groups},); got {scale.shape}')
     if not (np.all(np.isfinite(scale)) and np.all(scale > 0)):
       raise ValueError('scale must be finite and > 0')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  try:
-    totals = eng.predictive_group_sums(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                       num_samples, seed64, **kw)
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    totals = eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw)
     sc = None if scale is None else torch.from_numpy(scale).to(eng.device)
 
     def forecast(x, s, y_rank, k):
@@ -662,8 +659,6 @@ def ranking_summaries(features, observation_model, params, model_args, num_sampl
                  rank_pit=sub['rank_pit'], scored_rank_mean=sub['rank_mean'], scored_rank_quantiles=sub['rank_quantiles'],
                  scored_rank_probability=sub['rank_probability'])
     return out
-  finally:
-    eng.close()
 
 
 def extreme_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
@@ -686,56 +681,31 @@ def extreme_summaries(features, observation_model, params, model_args, num_sampl
     'exceed_probability' (n_rows,)                         share of the paths whose draw at the row is above its threshold
   The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells, ValueError beyond.
   weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
-  if num_samples > _native.SUMMARY_MAX_SAMPLES:
-    raise ValueError(f'num_samples={num_samples}: the extremes are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
-                     'sample paths')
-  levels = [float(v) for v in quantiles]
-  if any(not 0.0 <= v <= 1.0 for v in levels):
-    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  num_samples = _num_samples(num_samples, 'extremes')
+  levels = _quantile_levels(quantiles)
   seg_offsets, seg_rows = groups
   n_groups = len(seg_offsets) - 1
-  if num_samples * n_groups > _TOTALS_MAX_CELLS:
-    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the matrices are held whole on the device, at '
-                     f'most {_TOTALS_MAX_CELLS} cells')
+  _check_cells(num_samples, n_groups, 'matrices are')
   features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
   if threshold is not None:
-    threshold = np.ascontiguousarray(threshold, dtype=np.float64)
-    if threshold.shape != (n_rows,):
-      raise ValueError(f'threshold must hold one limit per row ({n_rows},); got {threshold.shape}')
-    if not np.all(np.isfinite(threshold)):
-      raise ValueError('threshold must be finite')
+    threshold = _row_threshold(threshold, features.shape[0])
   elif observed_count is not None:
     raise ValueError('observed_count needs a threshold')
-  observed = {}
-  for name, obs in (('max', observed_max), ('count', observed_count)):
-    if obs is not None:
-      observed[name] = np.ascontiguousarray(obs, dtype=np.float64)
-      if observed[name].shape != (n_groups,):
-        raise ValueError(f'observed_{name} must hold one value per group ({n_groups},); got {observed[name].shape}')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  try:
+  observed = {name: _per_group(f'observed_{name}', 'value', obs, n_groups)
+              for name, obs in (('max', observed_max), ('count', observed_count))}
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
     thr = None if threshold is None else threshold.astype(np.float32)
-    ext = eng.predictive_group_extremes(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                        num_samples, seed64, threshold=thr, **kw)
+    ext = eng.predictive_group_extremes(loc, aux, seg_offsets, seg_rows, num_samples, seed64, threshold=thr, **kw)
     out = {'peak_probability': ext['peak_count'].cpu().numpy().astype(np.float64) / num_samples}
     for name in ('max', 'count') if thr is not None else ('max',):
-      y = torch.from_numpy(observed[name]).to(eng.device) if name in observed else None
+      y = None if observed[name] is None else torch.from_numpy(observed[name]).to(eng.device)
       for k, v in eng.sample_summaries(ext[name], y, levels).items():
         out[f'{name}_{k}'] = v.cpu().numpy()
     if thr is not None:
       out['exceed_any'] = (ext['count'] > 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
       out['exceed_probability'] = ext['exceed_count'].cpu().numpy().astype(np.float64) / num_samples
     return out
-  finally:
-    eng.close()
 
 
 EPISODE_SERIES = ('longest', 'spells', 'onset_step')
@@ -761,54 +731,30 @@ def episode_summaries(features, observation_model, params, model_args, num_sampl
     'no_episode' (G,)                 no_episode_count / num_samples = 1 - the group's sum of onset_probability
   The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells, ValueError beyond.
   weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
-  num_samples = int(num_samples)
-  if num_samples < 1:
-    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
-  if num_samples > _native.SUMMARY_MAX_SAMPLES:
-    raise ValueError(f'num_samples={num_samples}: the episodes are summarised from at most {_native.SUMMARY_MAX_SAMPLES} '
-                     'sample paths')
-  levels = [float(v) for v in quantiles]
-  if any(not 0.0 <= v <= 1.0 for v in levels):
-    raise ValueError(f'quantiles must lie in [0, 1]; got {levels}')
+  num_samples = _num_samples(num_samples, 'episodes')
+  levels = _quantile_levels(quantiles)
   seg_offsets, seg_rows = groups
   n_groups = len(seg_offsets) - 1
-  if num_samples * n_groups > _TOTALS_MAX_CELLS:
-    raise ValueError(f'{num_samples} sample paths x {n_groups} groups: the matrices are held whole on the device, at '
-                     f'most {_TOTALS_MAX_CELLS} cells')
+  _check_cells(num_samples, n_groups, 'matrices are')
   features = np.asarray(features, dtype=np.float64)
-  n_rows = features.shape[0]
   if threshold is None:
     raise ValueError('threshold is required: one limit per row')
-  threshold = np.ascontiguousarray(threshold, dtype=np.float64)
-  if threshold.shape != (n_rows,):
-    raise ValueError(f'threshold must hold one limit per row ({n_rows},); got {threshold.shape}')
-  if not np.all(np.isfinite(threshold)):
-    raise ValueError('threshold must be finite')
-  observed = {}
-  for name, obs in zip(EPISODE_SERIES, (observed_longest, observed_spells, observed_onset_step)):
-    if obs is not None:
-      observed[name] = np.ascontiguousarray(obs, dtype=np.float64)
-      if observed[name].shape != (n_groups,):
-        raise ValueError(f'observed_{name} must hold one value per group ({n_groups},); got {observed[name].shape}')
-  _, cum = mixture_weights(weights, params, ensemble_dims)
-  kw = {} if cum is None else {'cum_weights': cum}
-  seed64 = _native.seed_to_u64(seed)
-  net, eng, _, loc_all, aux_all = _ensemble_forecast(
-      features, observation_model, params, model_args, ensemble_dims, compute_dtype)
-  try:
-    ep = eng.predictive_group_episodes(loc_all.reshape(-1, n_rows), aux_all.reshape(-1, 3), seg_offsets, seg_rows,
-                                       num_samples, seed64, threshold.astype(np.float32), **kw)
+  threshold = _row_threshold(threshold, features.shape[0])
+  observed = {name: _per_group(f'observed_{name}', 'value', obs, n_groups)
+              for name, obs in zip(EPISODE_SERIES, (observed_longest, observed_spells, observed_onset_step))}
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    ep = eng.predictive_group_episodes(loc, aux, seg_offsets, seg_rows, num_samples, seed64,
+                                       threshold.astype(np.float32), **kw)
     out = {'onset_count': ep['onset_count'].cpu().numpy().astype(np.int64),
            'no_episode_count': (ep['longest'] == 0).sum(dim=0).cpu().numpy().astype(np.int64)}
     out['onset_probability'] = out['onset_count'].astype(np.float64) / num_samples
     out['no_episode'] = out['no_episode_count'].astype(np.float64) / num_samples
     for name in EPISODE_SERIES:
-      y = torch.from_numpy(observed[name]).to(eng.device) if name in observed else None
+      y = None if observed[name] is None else torch.from_numpy(observed[name]).to(eng.device)
       for k, v in eng.sample_summaries(ep[name], y, levels).items():
         out[f'{name}_{k}'] = v.cpu().numpy()
     return out
-  finally:
-    eng.close()
 
 
 # ---------------------------------------------------------------------------

@@ -35,6 +35,7 @@ Differences a caller can see:
 
 from __future__ import annotations
 
+import types
 from collections.abc import Sequence
 
 import numpy as np
@@ -486,20 +487,64 @@ class BayesianNeuralFieldEstimator:
     The same (seed, table) gives the same numbers whatever num_samples is asked for (path s does not change).
     weights (the shape of `score(...)['member_log_prob']`, e.g. `stacking_weights(...)['weights']`): a path draws its
     member with these probabilities instead of equal ones.  None: equal weights, nothing changes."""
+    f = self._paths('predict_samples', table, group_by, num_samples, seed, weights, tag='')
+    out = f.run(inference.sample_predictive)
+    return out if group_by is None else (out, f.keys)
+
+  def _paths(self, what, table, group_by, num_samples, seed, weights, noun=None, tag=None, target=False,
+             threshold=None, needs_threshold=None, ordered=False, order_by=None):
+    """The front of every method that works on sample paths, its stages in the one order all of them check in: fitted;
+    the target column (target=True: a score_* method); the sample count, capped where `noun` names what
+    bnf_sample_summaries summarises; the per-row threshold (needs_threshold True: required, False: optional, None: the
+    method has none); the member weights; the grouping (group_by=None: none; ordered=True: the rows of a group in the
+    order of `order_by`, None = the time column).  All of it ValueError before any GPU work.
+    -> namespace: y, thr, keys, seg_offsets, seg_rows, and run(fn, **particular): the call of the inference function
+    `fn` at the rows of `table` with the arguments all of them share plus its particular ones."""
     if self.params_ is None:
-      raise ValueError('predict_samples before fit')
+      raise ValueError(f'{what} before fit')
+    tag = f'{what}: ' if tag is None else tag
+    y = self._targets(what, table) if target else None
     if int(num_samples) < 1:
-      raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+      raise ValueError(f'{tag}num_samples={num_samples}: need at least one sample path')
+    if noun is not None and int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{tag}num_samples={num_samples}: the {noun} are summarised from at most '
+                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
+    thr = None if needs_threshold is None else self._row_threshold(what, table, threshold, needs_threshold)
     kw = self._weights_kw(weights)
-    groups = keys = None
-    if group_by is not None:
+    keys = seg_offsets = seg_rows = None
+    if ordered:
+      keys, seg_offsets, seg_rows = group_rows_ordered(
+          table, group_by, self.data_handler._time_column if order_by is None else order_by)
+    elif group_by is not None:
       keys, seg_offsets, seg_rows = group_rows(table, group_by)
-      groups = (seg_offsets, seg_rows)
-    rows = self.data_handler.get_test(table)
-    out = inference.sample_predictive(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=groups, compute_dtype=self.compute_dtype, **kw)
-    return out if group_by is None else (out, keys)
+
+    def run(fn, **particular):
+      rows = self.data_handler.get_test(table)
+      return fn(rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
+                ensemble_dims=self._ensemble_dims, groups=None if keys is None else (seg_offsets, seg_rows),
+                compute_dtype=self.compute_dtype, **particular, **kw)
+
+    return types.SimpleNamespace(y=y, thr=thr, keys=keys, seg_offsets=seg_offsets, seg_rows=seg_rows, run=run)
+
+  @staticmethod
+  def _row_threshold(what, table, threshold, required):
+    """`threshold`, a scalar or one limit per row of `table` -> (len(table),) float64 holding float32 values (the draws
+    are float32: compared at that precision); None stays None unless `required`."""
+    if threshold is None:
+      if required:
+        raise ValueError(f'{what}: threshold is required: a number or one number per row of the table')
+      return None
+    try:
+      thr = np.asarray(threshold, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'{what}: threshold must be a number or one number per row of the table') from e
+    if thr.ndim == 0:
+      thr = np.full(len(table), float(thr))
+    if thr.shape != (len(table),):
+      raise ValueError(f'{what}: threshold must be a scalar or hold one limit per row ({len(table)},); got {thr.shape}')
+    if not np.all(np.isfinite(thr)):
+      raise ValueError(f'{what}: threshold must be finite')
+    return thr.astype(np.float32).astype(np.float64)
 
   def _weights_kw(self, weights):
     """{} for weights=None (the callee is called as before), else the checked weights as a keyword argument."""
@@ -542,9 +587,10 @@ class BayesianNeuralFieldEstimator:
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
-    `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking` (weights=...) and scored on
-    another table by `weighted_log_density`; they are taken by the marginal forecast as well: `predict` and `score`
-    (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.  `fit` is unchanged."""
+    `predict_episodes`, `score_episodes`, `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking`
+    (weights=...) and scored on another table by `weighted_log_density`; they are taken by the marginal forecast as well:
+    `predict` and `score` (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.
+    `fit` is unchanged."""
     if self.params_ is None:
       raise ValueError('stacking_weights before fit')
     res = self._stack('stacking_weights', table, None, max_iter, tol)
@@ -593,14 +639,8 @@ class BayesianNeuralFieldEstimator:
       raise ValueError('score before fit')
     if rps and self.observation_model == 'NORMAL':
       raise ValueError("score: rps=True is for the count observation models (NB, ZINB); NORMAL is scored by 'crps'")
-    if self.target_col not in table.columns:
-      raise ValueError(f'score: the target column {self.target_col!r} is not among the columns of the table')
-    y = np.asarray(table[self.target_col].values, dtype=np.float64)
-    if np.isinf(y).any():
-      raise ValueError('score: infinite targets')
+    y = self._targets('score', table)
     seen = y[np.isfinite(y)]
-    if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
-      raise ValueError(f'score: the {self.observation_model} observation model takes non-negative integer targets')
     kw = self._weights_kw(weights)
     rows = self.data_handler.get_test(table)
     out = inference.score_predictive(
@@ -616,32 +656,14 @@ class BayesianNeuralFieldEstimator:
       out['mean_rps'] = float(np.mean(out['rps'][kept], dtype=np.float64)) if kept.any() else float('nan')
     return out
 
-  def _total_summaries(self, what, table, group_by, quantiles, num_samples, seed, target=None, energy=False,
-                       weights=None):
-    if int(num_samples) < 1:
-      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
-    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
-      raise ValueError(f'{what}: num_samples={num_samples}: the totals are summarised from at most '
-                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
-    kw = self._weights_kw(weights)
-    keys, seg_offsets, seg_rows = group_rows(table, group_by)
-    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
-    rows = self.data_handler.get_test(table)
-    out = inference.total_summaries(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, quantiles=tuple(quantiles),
-        energy=bool(energy), compute_dtype=self.compute_dtype, **kw)
-    return out, keys, observed
-
   def predict_totals(self, table, group_by, quantiles=(0.5,), num_samples=1000, seed=0, weights=None):
     """Mean and quantile bands of the group totals of `predict_samples(table, num_samples, seed, group_by=group_by)`,
     summarised on the GPU: the (num_samples, G) matrix of totals never leaves the device.  -> (mean (G,), [one (G,) array
     per level, numpy's default 'linear' quantile of the sampled totals], keys) with keys as in `predict_samples`.
     num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('predict_totals before fit')
-    out, keys, _ = self._total_summaries('predict_totals', table, group_by, quantiles, num_samples, seed, weights=weights)
-    return out['mean'], [out['quantiles'][i] for i in range(out['quantiles'].shape[0])], keys
+    f = self._paths('predict_totals', table, group_by, num_samples, seed, weights, noun='totals')
+    out = f.run(inference.total_summaries, quantiles=tuple(quantiles), energy=False)
+    return out['mean'], [out['quantiles'][i] for i in range(out['quantiles'].shape[0])], f.keys
 
   def score_totals(self, table, group_by, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0, energy=True,
                    weights=None):
@@ -657,52 +679,22 @@ class BayesianNeuralFieldEstimator:
       'energy_score'  energy=True: the energy score of the joint paths over the scored groups, one number for the
                       whole vector of totals (num_samples^2 G / 2 differences)
     num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('score_totals before fit')
-    if self.target_col not in table.columns:
-      raise ValueError(f'score_totals: the target column {self.target_col!r} is not among the columns of the table')
-    y = np.asarray(table[self.target_col].values, dtype=np.float64)
-    if np.isinf(y).any():
-      raise ValueError('score_totals: infinite targets')
-    seen = y[np.isfinite(y)]
-    if self.observation_model != 'NORMAL' and (np.any(seen < 0) or np.any(seen != np.floor(seen))):
-      raise ValueError(f'score_totals: the {self.observation_model} observation model takes non-negative integer targets')
-    out, keys, observed = self._total_summaries(
-        'score_totals', table, group_by, quantiles, num_samples, seed, target=y, energy=energy, weights=weights)
+    f = self._paths('score_totals', table, group_by, num_samples, seed, weights, noun='totals', target=True)
+    observed = group_target_sums(f.y, f.seg_offsets, f.seg_rows)
+    out = f.run(inference.total_summaries, observed=observed, quantiles=tuple(quantiles), energy=bool(energy))
     scored = ~np.isnan(observed)
-    out.update(keys=keys, observed=observed, n=int(scored.sum()))
+    out.update(keys=f.keys, observed=observed, n=int(scored.sum()))
     out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')
     return out
 
-  def _extreme_summaries(self, what, table, group_by, threshold, quantiles, num_samples, seed, target=None, weights=None):
-    if int(num_samples) < 1:
-      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
-    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
-      raise ValueError(f'{what}: num_samples={num_samples}: the extremes are summarised from at most '
-                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
-    thr = None
-    if threshold is not None:
-      try:
-        thr = np.asarray(threshold, dtype=np.float64)
-      except (TypeError, ValueError) as e:
-        raise ValueError(f'{what}: threshold must be a number or one number per row of the table') from e
-      if thr.ndim == 0:
-        thr = np.full(len(table), float(thr))
-      if thr.shape != (len(table),):
-        raise ValueError(f'{what}: threshold must be a scalar or hold one limit per row ({len(table)},); got {thr.shape}')
-      if not np.all(np.isfinite(thr)):
-        raise ValueError(f'{what}: threshold must be finite')
-      thr = thr.astype(np.float32).astype(np.float64)          # the draws are float32: compared at that precision
-    kw = self._weights_kw(weights)
-    keys, seg_offsets, seg_rows = group_rows(table, group_by)
-    observed = None if target is None else group_target_extremes(target, seg_offsets, seg_rows, thr)
-    rows = self.data_handler.get_test(table)
-    out = inference.extreme_summaries(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), threshold=thr,
-        observed_max=None if observed is None else observed[0], observed_count=None if observed is None else observed[2],
-        quantiles=tuple(quantiles), compute_dtype=self.compute_dtype, **kw)
-    res = {'keys': keys, 'max_mean': out['max_mean'], 'max_quantiles': out['max_quantiles'],
+  def _extreme_summaries(self, what, table, group_by, threshold, quantiles, num_samples, seed, weights, target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='extremes', target=target,
+                    threshold=threshold, needs_threshold=False)
+    thr = f.thr
+    observed = None if f.y is None else group_target_extremes(f.y, f.seg_offsets, f.seg_rows, thr)
+    out = f.run(inference.extreme_summaries, threshold=thr, observed_max=None if observed is None else observed[0],
+                observed_count=None if observed is None else observed[2], quantiles=tuple(quantiles))
+    res = {'keys': f.keys, 'max_mean': out['max_mean'], 'max_quantiles': out['max_quantiles'],
            'peak_probability': out['peak_probability']}
     if thr is not None:
       res.update(exceed_any=out['exceed_any'], exceed_count_mean=out['count_mean'],
@@ -724,11 +716,7 @@ class BayesianNeuralFieldEstimator:
       'exceed_count_mean' (G,)  'exceed_count_quantiles' (len(quantiles), G)   the number of rows of the group above
       'exceed_probability' (len(table),)   the share of the paths whose draw at the row is above its threshold
     num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('predict_extremes before fit')
-    res, _, _ = self._extreme_summaries('predict_extremes', table, group_by, threshold, quantiles, num_samples, seed,
-                                        weights=weights)
-    return res
+    return self._extreme_summaries('predict_extremes', table, group_by, threshold, quantiles, num_samples, seed, weights)[0]
 
   def score_extremes(self, table, group_by, threshold=None, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0,
                      weights=None):
@@ -747,11 +735,8 @@ class BayesianNeuralFieldEstimator:
       'brier' (G,)              (exceed_any - 1{observed_count > 0})^2
       'mean_count_crps', 'mean_brier'
     The target checks are those of `score_totals`."""
-    if self.params_ is None:
-      raise ValueError('score_extremes before fit')
-    y = self._targets('score_extremes', table)
     res, out, (obs_max, obs_row, obs_count) = self._extreme_summaries(
-        'score_extremes', table, group_by, threshold, quantiles, num_samples, seed, target=y, weights=weights)
+        'score_extremes', table, group_by, threshold, quantiles, num_samples, seed, weights, target=True)
     scored = ~np.isnan(obs_max)
     mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
     prob = np.where(scored, res['peak_probability'][np.maximum(obs_row, 0)], np.nan)
@@ -765,41 +750,18 @@ class BayesianNeuralFieldEstimator:
                  mean_count_crps=mean(out['count_crps']), mean_brier=mean(brier))
     return res
 
-  def _episode_summaries(self, what, table, group_by, threshold, order_by, quantiles, num_samples, seed, target=None,
-                         weights=None):
-    if int(num_samples) < 1:
-      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
-    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
-      raise ValueError(f'{what}: num_samples={num_samples}: the episodes are summarised from at most '
-                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
-    if threshold is None:
-      raise ValueError(f'{what}: threshold is required: a number or one number per row of the table')
-    try:
-      thr = np.asarray(threshold, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-      raise ValueError(f'{what}: threshold must be a number or one number per row of the table') from e
-    if thr.ndim == 0:
-      thr = np.full(len(table), float(thr))
-    if thr.shape != (len(table),):
-      raise ValueError(f'{what}: threshold must be a scalar or hold one limit per row ({len(table)},); got {thr.shape}')
-    if not np.all(np.isfinite(thr)):
-      raise ValueError(f'{what}: threshold must be finite')
-    thr = thr.astype(np.float32).astype(np.float64)            # the draws are float32: compared at that precision
-    kw = self._weights_kw(weights)
-    keys, seg_offsets, seg_rows = group_rows_ordered(
-        table, group_by, self.data_handler._time_column if order_by is None else order_by)
-    n_groups = len(keys)
-    if int(num_samples) * n_groups > inference._TOTALS_MAX_CELLS:
+  def _episode_summaries(self, what, table, group_by, threshold, order_by, quantiles, num_samples, seed, weights,
+                         target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='episodes', target=target,
+                    threshold=threshold, needs_threshold=True, ordered=True, order_by=order_by)
+    n_groups = len(f.keys)
+    if int(num_samples) * n_groups > inference._TOTALS_MAX_CELLS:      # before the host pass over the observed spells
       raise ValueError(f'{what}: {num_samples} sample paths x {n_groups} groups: the matrices are held whole on the '
                        f'device, at most {inference._TOTALS_MAX_CELLS} cells')
-    observed = None if target is None else group_target_episodes(target, seg_offsets, seg_rows, thr)
-    rows = self.data_handler.get_test(table)
+    observed = None if f.y is None else group_target_episodes(f.y, f.seg_offsets, f.seg_rows, f.thr)
     obs_kw = {} if observed is None else {f'observed_{k}': observed[k] for k in inference.EPISODE_SERIES}
-    out = inference.episode_summaries(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), threshold=thr, quantiles=tuple(quantiles),
-        compute_dtype=self.compute_dtype, **obs_kw, **kw)
-    res = {'keys': keys, 'onset_probability': out['onset_probability'], 'no_episode': out['no_episode']}
+    out = f.run(inference.episode_summaries, threshold=f.thr, quantiles=tuple(quantiles), **obs_kw)
+    res = {'keys': f.keys, 'onset_probability': out['onset_probability'], 'no_episode': out['no_episode']}
     for name in inference.EPISODE_SERIES:
       res[f'{name}_mean'], res[f'{name}_quantiles'] = out[f'{name}_mean'], out[f'{name}_quantiles']
     return res, out, observed
@@ -820,11 +782,8 @@ class BayesianNeuralFieldEstimator:
       'onset_probability' (len(table),)   the share of the paths in which the row is its group's first row above
       'no_episode' (G,)          the share of the paths that never go above: 1 - the group's sum of 'onset_probability'
     num_samples <= 16,384.  weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('predict_episodes before fit')
-    res, _, _ = self._episode_summaries('predict_episodes', table, group_by, threshold, order_by, quantiles, num_samples,
-                                        seed, weights=weights)
-    return res
+    return self._episode_summaries('predict_episodes', table, group_by, threshold, order_by, quantiles, num_samples, seed,
+                                   weights)[0]
 
   def score_episodes(self, table, group_by, threshold, order_by=None, quantiles=(0.025, 0.5, 0.975), num_samples=1000,
                      seed=0, weights=None):
@@ -841,11 +800,8 @@ class BayesianNeuralFieldEstimator:
                                  'no_episode' when nothing was observed above; NaN where not scored
       'n'                        number of groups scored       'mean_onset_row_probability'
     The target checks are those of `score_totals`."""
-    if self.params_ is None:
-      raise ValueError('score_episodes before fit')
-    y = self._targets('score_episodes', table)
     res, out, observed = self._episode_summaries(
-        'score_episodes', table, group_by, threshold, order_by, quantiles, num_samples, seed, target=y, weights=weights)
+        'score_episodes', table, group_by, threshold, order_by, quantiles, num_samples, seed, weights, target=True)
     scored = ~np.isnan(observed['longest'])
     mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
     first = observed['first_row']
@@ -859,19 +815,13 @@ class BayesianNeuralFieldEstimator:
       res[f'mean_{name}_crps'] = mean(out[f'{name}_crps'])
     return res
 
-  def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=None, p=0.5,
+  def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=False, p=0.5,
                             pair_weights=None, matrices=True):
-    if int(num_samples) < 1:
-      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
-    kw = self._weights_kw(weights)
-    keys, seg_offsets, seg_rows = group_rows(table, group_by)
-    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
-    rows = self.data_handler.get_test(table)
-    out = inference.dependence_summaries(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, p=p,
-        pair_weights=pair_weights, matrices=bool(matrices), compute_dtype=self.compute_dtype, **kw)
-    res = {'keys': keys, 'mean': out['mean']}
+    f = self._paths(what, table, group_by, num_samples, seed, weights, target=target)
+    observed = None if f.y is None else group_target_sums(f.y, f.seg_offsets, f.seg_rows)
+    out = f.run(inference.dependence_summaries, observed=observed, p=p, pair_weights=pair_weights,
+                matrices=bool(matrices))
+    res = {'keys': f.keys, 'mean': out['mean']}
     if 'covariance' in out:
       cov = out['covariance']
       std = np.sqrt(np.diagonal(cov))
@@ -896,10 +846,7 @@ class BayesianNeuralFieldEstimator:
                            std is 0, 1 on the rest of the diagonal
     At most 4,096 groups, and num_samples * G <= 2^28.  weights: member weights of the sample paths as in
     `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('predict_dependence before fit')
-    res, _, _ = self._dependence_summaries('predict_dependence', table, group_by, num_samples, seed, weights)
-    return res
+    return self._dependence_summaries('predict_dependence', table, group_by, num_samples, seed, weights)[0]
 
   def score_dependence(self, table, group_by, p=0.5, pair_weights=None, matrices=True, num_samples=1000, seed=0,
                        weights=None):
@@ -919,11 +866,8 @@ class BayesianNeuralFieldEstimator:
     matrices=False returns the score alone and lifts the cap of 4,096 groups (pair_weights keep it);
     num_samples * G <= 2^28 either way.  The target checks are those of `score_totals`.  weights: member weights of the
     sample paths as in `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('score_dependence before fit')
-    y = self._targets('score_dependence', table)
     res, out, observed = self._dependence_summaries(
-        'score_dependence', table, group_by, num_samples, seed, weights, target=y, p=p, pair_weights=pair_weights,
+        'score_dependence', table, group_by, num_samples, seed, weights, target=True, p=p, pair_weights=pair_weights,
         matrices=matrices)
     scored = ~np.isnan(observed)
     n = int(scored.sum())
@@ -965,22 +909,12 @@ class BayesianNeuralFieldEstimator:
       raise ValueError(f'{what}: per must be constant within every group')
     return lo
 
-  def _ranking_summaries(self, what, table, group_by, top_k, per, quantiles, num_samples, seed, weights, target=None):
-    if int(num_samples) < 1:
-      raise ValueError(f'{what}: num_samples={num_samples}: need at least one sample path')
-    if int(num_samples) > inference._native.SUMMARY_MAX_SAMPLES:
-      raise ValueError(f'{what}: num_samples={num_samples}: the ranks are summarised from at most '
-                       f'{inference._native.SUMMARY_MAX_SAMPLES} sample paths')
-    kw = self._weights_kw(weights)
-    keys, seg_offsets, seg_rows = group_rows(table, group_by)
-    scale = self._per_group(what, table, per, seg_offsets, seg_rows)
-    observed = None if target is None else group_target_sums(target, seg_offsets, seg_rows)
-    rows = self.data_handler.get_test(table)
-    out = inference.ranking_summaries(
-        rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-        ensemble_dims=self._ensemble_dims, groups=(seg_offsets, seg_rows), observed=observed, scale=scale, top_k=top_k,
-        quantiles=tuple(quantiles), compute_dtype=self.compute_dtype, **kw)
-    return out, keys, observed
+  def _ranking_summaries(self, what, table, group_by, top_k, per, quantiles, num_samples, seed, weights, target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='ranks', target=target)
+    scale = self._per_group(what, table, per, f.seg_offsets, f.seg_rows)
+    observed = None if f.y is None else group_target_sums(f.y, f.seg_offsets, f.seg_rows)
+    out = f.run(inference.ranking_summaries, observed=observed, scale=scale, top_k=top_k, quantiles=tuple(quantiles))
+    return out, f.keys, observed
 
   @staticmethod
   def _ranking_result(keys, mean, quant, prob):
@@ -1005,8 +939,6 @@ class BayesianNeuralFieldEstimator:
     a population: the groups are then ranked by total / per.  At most 16,384 groups, num_samples <= 16,384,
     num_samples * G <= 2^28, 1 <= top_k <= G and top_k * G <= 2^24.  weights: member weights of the sample paths as in
     `predict_samples`; None: equal weights."""
-    if self.params_ is None:
-      raise ValueError('predict_ranking before fit')
     out, keys, _ = self._ranking_summaries('predict_ranking', table, group_by, top_k, per, quantiles, num_samples, seed,
                                            weights)
     return self._ranking_result(keys, out['rank_mean'], out['rank_quantiles'], out['rank_probability'])
@@ -1029,11 +961,8 @@ class BayesianNeuralFieldEstimator:
                                beyond top_k
       'n'                      groups scored          'mean_rank_crps'  mean of 'rank_crps' over them
     The target checks are those of `score_totals`; the limits and `per`, `weights` those of `predict_ranking`."""
-    if self.params_ is None:
-      raise ValueError('score_ranking before fit')
-    y = self._targets('score_ranking', table)
     out, keys, observed = self._ranking_summaries('score_ranking', table, group_by, top_k, per, quantiles, num_samples,
-                                                  seed, weights, target=y)
+                                                  seed, weights, target=True)
     prob = out['scored_rank_probability']
     res = self._ranking_result(keys, out['scored_rank_mean'], out['scored_rank_quantiles'], prob)
     scored = ~np.isnan(observed)
