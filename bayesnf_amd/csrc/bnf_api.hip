@@ -36,6 +36,7 @@
 #include "bnf_sampling.h"
 #include "bnf_extremes.h"
 #include "bnf_episodes.h"
+#include "bnf_cumulative.h"
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
@@ -2208,6 +2209,45 @@ int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* 
                        cum_weights, threshold, (EpPiece*)work, o);
     hipLaunchKernelGGL(k_predictive_group_episodes_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
                        (int32_t)n_groups, n_rows, n, (EpPiece*)work, o);
+  });
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- running totals of the sample paths and when they pass a level (bnf_cumulative.h) ----
+// The launch shape of k_predictive_group_cumulative.  Only the block of a tile in which a group STARTS has work, and at
+// most min(tiles, groups) tiles have one; a table that is one long group has a single working tile and is parallel over
+// the samples alone.  So grid.y is pred_grid's 16384 / gx, raised until min(tiles, groups) x grid.y reaches
+// kCumMinBlocks = 2048 blocks (256 CUs x 8), never above the samples.  A block that owns nothing costs one bisection.
+constexpr int64_t kCumMinBlocks = 2048;
+static dim3 cum_grid(int64_t R, int64_t G, int64_t S) {
+  const int64_t gx = cdiv(R, kPredTile);
+  const int64_t want = std::max<int64_t>(std::max<int64_t>(1, 16384 / gx), cdiv(kCumMinBlocks, std::min(gx, G)));
+  return dim3((unsigned)gx, (unsigned)std::min<int64_t>(std::min<int64_t>(S, 65535), want));
+}
+
+int bnf_predictive_group_cumulative(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                    const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
+                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                    const double* cum_weights, const double* level, double* out_total,
+                                    double* out_running, double* out_cross_step, int32_t* out_cross_row,
+                                    uint32_t* cross_count, uint32_t* above_count) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  if (!out_total) return fail(BNF_ERR_INVALID, "out_total is required");
+  if (!level && (out_cross_step || out_cross_row || cross_count || above_count))
+    return fail(BNF_ERR_INVALID, "out_cross_step, out_cross_row, cross_count and above_count need a level");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // groups without a row: total 0, cross_step 0 (censored at 0 steps), cross_row -1
+  const size_t cells = (size_t)n_samples * (size_t)n_groups;
+  HIPCHK(hipMemsetAsync(out_total, 0, cells * sizeof(double), h->stream));
+  if (out_cross_step) HIPCHK(hipMemsetAsync(out_cross_step, 0, cells * sizeof(double), h->stream));
+  if (out_cross_row) HIPCHK(hipMemsetAsync(out_cross_row, 0xff, cells * sizeof(int32_t), h->stream));
+  const CumOut o{level, out_total, out_running, out_cross_step, out_cross_row, cross_count, above_count};
+  with_obs(h, [&](auto obs) {
+    hipLaunchKernelGGL((k_predictive_group_cumulative<decltype(obs)::value>), cum_grid(n_rows, n_groups, n_samples),
+                       dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, seg_offsets, seg_rows,
+                       (int32_t)n_groups, n_samples, seed, row0, sample0, cum_weights, o);
   });
   HIPCHK(hipGetLastError());
   return BNF_OK;

@@ -464,6 +464,45 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work`, `off`, `rows`, `thr` and `cum` are released on return
     return out
 
+  def predictive_group_cumulative(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
+                                  level=None, running=False, per_row=True, cum_weights=None, row0=0, sample0=0) -> dict:
+    """Running totals of the same sample paths, per group of rows, and when they pass a level (include/bnf.h
+    bnf_predictive_group_cumulative), without materialising the draws; loc, aux, seg_offsets, seg_rows, row0, sample0 and
+    cum_weights as for `predictive_group_sums`.  TIME is the order of the positions of seg_rows inside a group
+    (`inference.csr_ordered`).  The run at a position is the f64 sum of the group's draws up to and including it; an
+    entry of seg_rows outside [0, R) takes no part (the run is carried, it is not a step); a NaN draw makes every later
+    run of its group NaN and counts as a step.  level (G,) f64, one per group: the crossing position is the first
+    participating one with run > level (strict, false for NaN).  -> dict of device tensors:
+      'total' (n_samples, G) f64        the run at the group's last position, 0 for a group without rows
+      'running' (n_samples, R) f64      running=True: the run, column = POSITION of seg_rows (not table row)
+      'cross_step' (n_samples, G) f64   with `level`: participating positions before the crossing one; all of them if none
+      'cross_row' (n_samples, G) int32  with `level`: the table row of the crossing position, -1 if none
+      'cross_count' (R,) int32          with `level`, per_row=True: the paths in which the row is its group's crossing row
+      'above_count' (R,) int32          with `level`, per_row=True: the paths whose run at the row's position is > the level
+    One kernel without a work buffer: a group longer than a tile is finished by one block per path, so a table that is
+    one long group is parallel over the paths only (profiles/group_cumulative.md).  Deterministic: the same call gives
+    the same bits, whatever n_samples, the cut into calls (sample0) and the outputs asked for."""
+    loc, aux, off, rows, M, R, G = self._group_inputs(loc, aux, seg_offsets, seg_rows)
+    lvl = None if level is None else self._as_f64(level, (G,), 'level')
+    n_samples = int(n_samples)
+    out = {'total': torch.empty((n_samples, G), dtype=torch.float64, device=self.device)}
+    if running:
+      out['running'] = torch.empty((n_samples, R), dtype=torch.float64, device=self.device)
+    if lvl is not None:
+      out['cross_step'] = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+      out['cross_row'] = torch.empty((n_samples, G), dtype=torch.int32, device=self.device)
+      if per_row:                           # the library adds to these: zeroed here
+        out['cross_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+        out['above_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_group_cumulative(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(lvl), _ptr(out['total']),
+        _ptr(out.get('running')), _ptr(out.get('cross_step')), _ptr(out.get('cross_row')), _ptr(out.get('cross_count')),
+        _ptr(out.get('above_count'))), 'bnf_predictive_group_cumulative')
+    torch.cuda.synchronize(self.device)     # `off`, `rows`, `lvl` and `cum` are released on return
+    return out
+
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
                         lpd=True, pit=True, weights=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),

@@ -757,6 +757,98 @@ def episode_summaries(features, observation_model, params, model_args, num_sampl
     return out
 
 
+def _group_level(level, n_groups):
+  """A (G,) finite level as contiguous float64; None stays None."""
+  if level is None:
+    return None
+  try:
+    level = np.ascontiguousarray(level, dtype=np.float64)
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'level must be an array of numbers of shape ({n_groups},)') from e
+  if level.shape != (n_groups,):
+    raise ValueError(f'level must hold one level per group ({n_groups},); got {level.shape}')
+  if not np.all(np.isfinite(level)):
+    raise ValueError('level must be finite')
+  return level
+
+
+def cumulative_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                         level=None, curve=True, observed_total=None, observed_running=None, observed_cross_step=None,
+                         quantiles=(), compute_dtype=None, weights=None):
+  """Running totals of the joint sample paths and when they pass a level, summarised and scored on the GPU: per path and
+  group the cumulative curve over the group's rows in time order, its last value and the step at which it first lies
+  above the group's level are formed without materialising the draws (include/bnf.h bnf_predictive_group_cumulative);
+  the matrices stay on the device and go through bnf_sample_summaries.  groups = (seg_offsets, seg_rows) with the rows
+  of a group in TIME order (`csr_ordered`); level (G,) finite, any sign, compared with strict >; observed_total /
+  observed_cross_step (G,) and observed_running (n_rows,), per TABLE ROW, the observed values, NaN where not to be scored.
+  -> dict of float64 numpy arrays:
+    'total_mean' (G,)  'total_quantiles' (len(quantiles), G)     numpy's default 'linear' rule
+    'total_crps' (G,)  'total_pit' (2, G)                        with observed_total, as `total_summaries` forms them
+  with curve=True, per table row (NaN at a row no position of seg_rows names):
+    'running_mean' (n_rows,)  'running_quantiles' (len(quantiles), n_rows)   of the running total at the row: the band
+                                                                 of the joint paths, which no marginal forecast gives
+    'running_crps' (n_rows,)  'running_pit' (2, n_rows)          with observed_running
+  and with `level`:
+    'cross_step_mean', 'cross_step_quantiles', ('cross_step_crps', 'cross_step_pit' with observed_cross_step)   of the
+                                      number of steps before the crossing row, censored at the group's size
+    'crossing_probability' (n_rows,)  share of the paths in which the row is where its group first lies above its level
+    'above_probability' (n_rows,)     share of the paths whose running total at the row lies above the level
+    'never' (G,)                      share of the paths that never cross (cross_row < 0, counted on the device) = 1 - the
+                                      group's sum of crossing_probability
+  The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells; curve=True holds the
+  (num_samples, n_rows) curves whole as well: num_samples * n_rows <= 2^28.  ValueError beyond, before any GPU work.
+  A group longer than a tile of 1,024 rows is parallel over the paths only (profiles/group_cumulative.md:
+  one group of 10^6 rows and 1,000 paths takes 1.3 times the group sums).
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = _num_samples(num_samples, 'running totals')
+  levels = _quantile_levels(quantiles)
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  _check_cells(num_samples, n_groups)
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  if curve:
+    _check_cells(num_samples, n_rows, 'running totals are')
+  level = _group_level(level, n_groups)
+  if level is None and observed_cross_step is not None:
+    raise ValueError('observed_cross_step needs a level')
+  if not curve and observed_running is not None:
+    raise ValueError('observed_running needs curve=True')
+  observed = {'total': _per_group('observed_total', 'value', observed_total, n_groups),
+              'cross_step': _per_group('observed_cross_step', 'value', observed_cross_step, n_groups)}
+  if observed_running is not None:
+    observed_running = np.ascontiguousarray(observed_running, dtype=np.float64)
+    if observed_running.shape != (n_rows,):
+      raise ValueError(f'observed_running must hold one value per row ({n_rows},); got {observed_running.shape}')
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    cu = eng.predictive_group_cumulative(loc, aux, seg_offsets, seg_rows, num_samples, seed64, level=level,
+                                         running=bool(curve), **kw)
+    out = {}
+    for name in ('total', 'cross_step') if level is not None else ('total',):
+      y = None if observed[name] is None else torch.from_numpy(observed[name]).to(eng.device)
+      for k, v in eng.sample_summaries(cu[name], y, levels).items():
+        out[f'{name}_{k}'] = v.cpu().numpy()
+    if curve:                                   # column = position: back to table rows through seg_rows
+      pos_rows = np.asarray(seg_rows, dtype=np.int64)
+      named = (pos_rows >= 0) & (pos_rows < n_rows)
+      y = None
+      if observed_running is not None:
+        y_pos = np.full(pos_rows.shape, np.nan)
+        y_pos[named] = observed_running[pos_rows[named]]
+        y = torch.from_numpy(y_pos).to(eng.device)
+      for k, v in eng.sample_summaries(cu['running'], y, levels).items():
+        v = v.cpu().numpy()
+        by_row = np.full(v.shape, np.nan)
+        by_row[..., pos_rows[named]] = v[..., named]
+        out[f'running_{k}'] = by_row
+    if level is not None:
+      out['crossing_probability'] = cu['cross_count'].cpu().numpy().astype(np.float64) / num_samples
+      out['above_probability'] = cu['above_count'].cpu().numpy().astype(np.float64) / num_samples
+      out['never'] = (cu['cross_row'] < 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
+    return out
+
+
 # ---------------------------------------------------------------------------
 # scores of held-out observations
 # ---------------------------------------------------------------------------

@@ -319,6 +319,43 @@ def group_target_episodes(target, seg_offsets, seg_rows, threshold):
   return out
 
 
+def group_target_cumulative(target, seg_offsets, seg_rows, level=None):
+  """Observed running totals: per group of a CSR layout whose positions are in time order (`group_rows_ordered`), the
+  float64 cumulative sum of `target` (R,) along the group's positions -> dict:
+    'running' (R,) float64     per TABLE ROW: the running total at the row; NaN from the group's first NaN target on
+    'total' (G,) float64       the running total at the group's last row
+  and with `level` (G,), one per group, compared with strict >:
+    'cross_step' (G,) float64  the rows before the first one whose running total is above the level; the group's size if
+                               none (censored, as the forecast is)
+    'cross_row' (G,) int64     that table row, -1 if none
+  A group with a NaN target among its rows (and an empty one, which `group_rows` never makes) gives NaN in 'total' and
+  'cross_step' and -1 in 'cross_row': it is not scored."""
+  target = np.asarray(target, dtype=np.float64)
+  order = np.asarray(seg_rows, dtype=np.int64)
+  offsets = np.asarray(seg_offsets, dtype=np.int64)
+  n_groups = len(offsets) - 1
+  out = {'running': np.full(target.shape, np.nan), 'total': np.full(n_groups, np.nan)}
+  if level is not None:
+    level = np.asarray(level, dtype=np.float64)
+    out['cross_step'] = np.full(n_groups, np.nan)
+    out['cross_row'] = np.full(n_groups, -1, dtype=np.int64)
+  for g in range(n_groups):
+    a, b = offsets[g], offsets[g + 1]
+    if a == b:
+      continue
+    run = np.cumsum(target[order[a:b]])
+    out['running'][order[a:b]] = run
+    if np.isnan(run[-1]):
+      continue
+    out['total'][g] = run[-1]
+    if level is not None:
+      hit = np.flatnonzero(run > level[g])
+      out['cross_step'][g] = float(hit[0]) if hit.size else float(b - a)
+      if hit.size:
+        out['cross_row'][g] = order[a + hit[0]]
+  return out
+
+
 # ---------------------------------------------------------------------------
 # estimators
 # ---------------------------------------------------------------------------
@@ -587,7 +624,8 @@ class BayesianNeuralFieldEstimator:
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
-    `predict_episodes`, `score_episodes`, `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking`
+    `predict_episodes`, `score_episodes`, `predict_cumulative`, `score_cumulative`, `predict_dependence`,
+    `score_dependence`, `predict_ranking` and `score_ranking`
     (weights=...) and scored on another table by `weighted_log_density`; they are taken by the marginal forecast as well:
     `predict` and `score` (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.
     `fit` is unchanged."""
@@ -813,6 +851,127 @@ class BayesianNeuralFieldEstimator:
       res[f'observed_{name}'] = observed[name]
       res[f'{name}_crps'], res[f'{name}_pit'] = out[f'{name}_crps'], out[f'{name}_pit']
       res[f'mean_{name}_crps'] = mean(out[f'{name}_crps'])
+    return res
+
+  @staticmethod
+  def _group_level(what, table, level, seg_offsets, seg_rows):
+    """The level of every group from `level`: None, a scalar, a column of `table` or one value per table row; constant
+    within every group and finite, any sign -> (G,) float64 or None."""
+    if level is None:
+      return None
+    if isinstance(level, str):
+      if level not in table.columns:
+        raise ValueError(f'{what}: level: {level!r} is not among the columns of the table')
+      level = table[level].values
+    try:
+      v = np.asarray(level, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'{what}: level must be a number, a column of the table or one number per row') from e
+    if v.ndim == 0:
+      v = np.full(len(table), float(v))
+    if v.shape != (len(table),):
+      raise ValueError(f'{what}: level must be a scalar or hold one value per row ({len(table)},); got {v.shape}')
+    if not np.all(np.isfinite(v)):
+      raise ValueError(f'{what}: level must be finite')
+    ordered = v[np.asarray(seg_rows, dtype=np.int64)]
+    starts = np.asarray(seg_offsets[:-1], dtype=np.int64)
+    lo, hi = np.minimum.reduceat(ordered, starts), np.maximum.reduceat(ordered, starts)
+    if np.any(lo != hi):
+      raise ValueError(f'{what}: level must be constant within every group')
+    return lo
+
+  def _cumulative_summaries(self, what, table, group_by, level, order_by, quantiles, curve, num_samples, seed, weights,
+                            target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='running totals', target=target,
+                    ordered=True, order_by=order_by)
+    lvl = self._group_level(what, table, level, f.seg_offsets, f.seg_rows)
+    for n, held in ((len(f.keys), 'groups: the totals matrix is'), (len(table) if curve else 0, 'rows: the running totals are')):
+      if int(num_samples) * n > inference._TOTALS_MAX_CELLS:             # before the host pass over the observed curve
+        raise ValueError(f'{what}: {num_samples} sample paths x {n} {held} held whole on the device, at most '
+                         f'{inference._TOTALS_MAX_CELLS} cells')
+    observed = None if f.y is None else group_target_cumulative(f.y, f.seg_offsets, f.seg_rows, lvl)
+    obs_kw = {}
+    if observed is not None:
+      obs_kw['observed_total'] = observed['total']
+      if curve:
+        obs_kw['observed_running'] = observed['running']
+      if lvl is not None:
+        obs_kw['observed_cross_step'] = observed['cross_step']
+    out = f.run(inference.cumulative_summaries, level=lvl, curve=bool(curve), quantiles=tuple(quantiles), **obs_kw)
+    res = {'keys': f.keys, 'total_mean': out['total_mean'], 'total_quantiles': out['total_quantiles']}
+    if curve:
+      res.update(running_mean=out['running_mean'], running_quantiles=out['running_quantiles'])
+    if lvl is not None:
+      res.update(crossing_step_mean=out['cross_step_mean'], crossing_step_quantiles=out['cross_step_quantiles'],
+                 crossing_probability=out['crossing_probability'], above_probability=out['above_probability'],
+                 never=out['never'])
+    return res, out, observed
+
+  def predict_cumulative(self, table, group_by, level=None, order_by=None, quantiles=(0.5,), curve=True, num_samples=1000,
+                         seed=0, weights=None):
+    """Running totals of the sample paths of `predict_samples(table, num_samples, seed)`: the cumulative curve of every
+    group with its band, and when it passes a level, formed and summarised on the GPU (neither the draws nor the
+    matrices leave the device).  The band of a running total at a row cannot be taken from any marginal of `predict`: it
+    needs the joint paths.  These depend on the ORDER of a group's rows: `order_by=None` orders them by the time column
+    (feature_cols[0]), a column name by that column; ties keep table order.  level: a scalar, a column name or one value
+    per row, constant within every group and finite (any sign), in the units of the target column; a running total
+    crosses at the first row at which it is strictly above.  -> dict:
+      'keys'                     the groups, as in `predict_samples`
+      'total_mean' (G,)  'total_quantiles' (len(quantiles), G)   the group's total: the curve's last value
+    with curve=True (holds num_samples x len(table) values on the device, at most 2^28):
+      'running_mean' (len(table),)  'running_quantiles' (len(quantiles), len(table))   the running total at every row
+    and with `level`:
+      'crossing_step_mean' (G,)  'crossing_step_quantiles' (len(quantiles), G)   the rows before the crossing row; a path
+                                 that never crosses counts the group's size (censored at the horizon)
+      'crossing_probability' (len(table),)   the share of the paths in which the row is its group's crossing row
+      'above_probability' (len(table),)      the share of the paths whose running total at the row is above the level
+                                 (for NORMAL a curve can come back under it: this is not the running sum of the former)
+      'never' (G,)               the share of the paths that never cross: 1 - the group's sum of 'crossing_probability'
+    num_samples <= 16,384.  A group of more than 1,024 rows is worked on by one workgroup per path: with 1,000 paths a
+    table that is a single group of 10^6 rows takes 1.3 times the device time of its totals alone, with far fewer paths it
+    fills the device only in part (profiles/group_cumulative.md).
+    weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    return self._cumulative_summaries('predict_cumulative', table, group_by, level, order_by, quantiles, curve,
+                                      num_samples, seed, weights)[0]
+
+  def score_cumulative(self, table, group_by, level=None, order_by=None, quantiles=(0.025, 0.5, 0.975), curve=True,
+                       num_samples=1000, seed=0, weights=None):
+    """The forecast of `predict_cumulative` scored against the running totals observed in `table[target_col]`, on the
+    GPU.  -> the dict of `predict_cumulative` plus
+      'observed_total' (G,)      `group_target_cumulative` on the target; NaN when any row of the group has a NaN target:
+                                 such a group is not scored
+      'total_crps' (G,)  'total_pit' (2, G)   ensemble CRPS and the share of the sampled totals <= and < the observed one;
+                                 NaN where not scored
+      'n'                        number of groups scored       'mean_total_crps'  mean over them
+    with curve=True:
+      'observed_running' (len(table),)   the observed running total at the row; NaN from a group's first NaN target on
+      'running_crps' (len(table),)  'running_pit' (2, len(table))   the same scores row by row; NaN where not scored
+      'mean_running_crps'        mean over the scored rows
+    and with `level`:
+      'observed_crossing_step' (G,)  'observed_crossing_row' (G,)   censored as the forecast is; -1 if none (or not scored)
+      'crossing_step_crps' (G,)  'crossing_step_pit' (2, G)  'mean_crossing_step_crps'
+      'crossing_row_probability' (G,)   the forecast probability ('crossing_probability') of the observed crossing row, or
+                                 'never' when none was observed; NaN where not scored
+      'mean_crossing_row_probability'
+    The target checks are those of `score_totals`."""
+    res, out, observed = self._cumulative_summaries('score_cumulative', table, group_by, level, order_by, quantiles, curve,
+                                                    num_samples, seed, weights, target=True)
+    scored = ~np.isnan(observed['total'])
+    mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
+    res.update(observed_total=observed['total'], total_crps=out['total_crps'], total_pit=out['total_pit'],
+               n=int(scored.sum()), mean_total_crps=mean(out['total_crps']))
+    if curve:
+      rows = ~np.isnan(observed['running'])
+      res.update(observed_running=observed['running'], running_crps=out['running_crps'], running_pit=out['running_pit'],
+                 mean_running_crps=float(np.mean(out['running_crps'][rows], dtype=np.float64)) if rows.any() else float('nan'))
+    if 'cross_step' in observed:
+      row = observed['cross_row']
+      prob = np.where(row >= 0, res['crossing_probability'][np.maximum(row, 0)], res['never'])
+      prob = np.where(scored, prob, np.nan)
+      res.update(observed_crossing_step=observed['cross_step'], observed_crossing_row=row,
+                 crossing_step_crps=out['cross_step_crps'], crossing_step_pit=out['cross_step_pit'],
+                 mean_crossing_step_crps=mean(out['cross_step_crps']), crossing_row_probability=prob,
+                 mean_crossing_row_probability=mean(prob))
     return res
 
   def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=False, p=0.5,

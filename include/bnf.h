@@ -392,6 +392,51 @@ int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* 
                                   int32_t* out_longest_row, double* out_spells, double* out_onset_step,
                                   int32_t* out_first_row, int32_t* out_last_row, uint32_t* onset_count);
 
+/* RUNNING TOTALS of the same sample paths, per group of rows, and when they pass a level, without materialising the
+ * draws (the reference has no counterpart: it would loop over `.sample()` and cumsum on the host).  loc, aux,
+ * seg_offsets, seg_rows, row0, sample0 and cum_weights (NULL = equal weights) as for bnf_predictive_group_episodes.
+ * TIME is the order of the positions of seg_rows inside a group (inference.csr_ordered).  Per path s, group g and
+ * position p of g:
+ *   run[s][p] = the f64 sum of the draws at the participating positions of g up to and including p.  A draw is the f32
+ *     that bnf_predictive_samples writes for (seed, sample0 + s, row0 + row), bit for bit, widened to f64.
+ *   An entry of seg_rows outside [0, n_rows) takes no part: its run is the value carried so far (0 at a group's start)
+ *     and it is not a step.  A NaN draw takes part: it makes every later run of its group NaN, as a cumulative sum does,
+ *     and it counts as a step.
+ *   out_total DEVICE (n_samples, n_groups) f64, required: run at the group's last position; 0 for a group without a
+ *     participating position
+ *   out_running DEVICE (n_samples, n_rows) f64 or NULL: run, column = POSITION of seg_rows (not table row)
+ *   level DEVICE (n_groups,) f64 or NULL: one level per group.  The CROSSING POSITION of (s, g) is the first participating
+ *     position with run > level[g]; the comparison is strict, in f64, and false for NaN.  With a level, each skipped
+ *     when its pointer is NULL:
+ *   out_cross_step DEVICE (n_samples, n_groups) f64: the number of participating positions before the crossing position;
+ *     when the path never crosses, the number of participating positions of the group (censored at the horizon, never
+ *     NaN: bnf_sample_summaries takes the matrix)
+ *   out_cross_row DEVICE (n_samples, n_groups) int32: the TABLE ROW of the crossing position, -1 when the path never
+ *     crosses
+ *   cross_count, above_count DEVICE (n_rows,) uint32, ZEROED BY THE CALLER, added to with integer atomics only:
+ *     cross_count[r] += the number of paths in which r is its group's crossing row
+ *     above_count[r] += the number of paths with run > level at r's position
+ *     (the running total of a NORMAL handle can come back under the level: above_count is not the running sum of
+ *     cross_count)
+ * A group without a participating position reports total 0, cross_step 0, cross_row -1.
+ * One kernel over tiles of BNF_GROUP_TILE positions, no work buffer: a group that leaves its tile through the far edge
+ * is finished by the block of the tile it starts in, which walks on over the following tiles; no workgroup waits for
+ * another (bnf_cumulative.h).  A long group is therefore parallel over the samples only.
+ * DETERMINISM: no floating-point atomics; two calls give the same bits.  The bits of every output depend only on the
+ * seed, sample0 + s, row0, loc, aux, cum_weights, level and the CSR arrays: not on n_samples, on how the samples are cut
+ * into calls, on the launch geometry or on which output pointers are NULL.  They may depend on where a group lies on the
+ * position axis: the order of the f64 additions follows the tiling, as for bnf_predictive_group_sums.  For NB and ZINB
+ * every sum is an exact integer below 2^53, so the order plays no part.
+ * BNF_ERR_INVALID also for a NULL out_total, for any of out_cross_step, out_cross_row, cross_count, above_count non-NULL
+ * while level is NULL, and for n_members, n_rows, n_groups or n_samples < 1; nothing is written then.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+int bnf_predictive_group_cumulative(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                    const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
+                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                    const double* cum_weights, const double* level, double* out_total,
+                                    double* out_running, double* out_cross_step, int32_t* out_cross_row,
+                                    uint32_t* cross_count, uint32_t* above_count);
+
 /* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
  * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
  * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
