@@ -37,6 +37,7 @@
 #include "bnf_extremes.h"
 #include "bnf_episodes.h"
 #include "bnf_cumulative.h"
+#include "bnf_windows.h"
 #include "bnf_scoring.h"
 #include "bnf_rps.h"
 #include "bnf_totals.h"
@@ -2248,6 +2249,35 @@ int bnf_predictive_group_cumulative(bnf_handle* h, const float* loc, const float
     hipLaunchKernelGGL((k_predictive_group_cumulative<decltype(obs)::value>), cum_grid(n_rows, n_groups, n_samples),
                        dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, seg_offsets, seg_rows,
                        (int32_t)n_groups, n_samples, seed, row0, sample0, cum_weights, o);
+  });
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- moving-window totals of the sample paths (bnf_windows.h) ----
+// The launch shape is cum_grid's: only the block of a tile in which a group starts has work.
+int bnf_predictive_group_windows(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                 const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                 uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights, int32_t window,
+                                 const double* threshold, double* out_peak, int32_t* out_peak_row, double* out_window,
+                                 double* out_count, uint32_t* peak_count, uint32_t* exceed_count) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!seg_offsets || !seg_rows || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  if (!out_peak) return fail(BNF_ERR_INVALID, "out_peak is required");
+  if (window < 1) return fail(BNF_ERR_INVALID, "window must be >= 1 position; got %d", (int)window);
+  if (!threshold && (out_count || exceed_count))
+    return fail(BNF_ERR_INVALID, "out_count and exceed_count need a threshold");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // groups without a candidate window: peak NaN (all bits set), peak_row -1, count 0
+  const size_t cells = (size_t)n_samples * (size_t)n_groups;
+  HIPCHK(hipMemsetAsync(out_peak, 0xff, cells * sizeof(double), h->stream));
+  if (out_peak_row) HIPCHK(hipMemsetAsync(out_peak_row, 0xff, cells * sizeof(int32_t), h->stream));
+  if (out_count) HIPCHK(hipMemsetAsync(out_count, 0, cells * sizeof(double), h->stream));
+  const WinOut o{threshold, out_peak, out_peak_row, out_window, out_count, peak_count, exceed_count};
+  with_obs(h, [&](auto obs) {
+    hipLaunchKernelGGL((k_predictive_group_windows<decltype(obs)::value>), cum_grid(n_rows, n_groups, n_samples),
+                       dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, seg_offsets, seg_rows,
+                       (int32_t)n_groups, n_samples, seed, row0, sample0, cum_weights, window, o);
   });
   HIPCHK(hipGetLastError());
   return BNF_OK;

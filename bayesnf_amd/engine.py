@@ -503,6 +503,50 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `off`, `rows`, `lvl` and `cum` are released on return
     return out
 
+  def predictive_group_windows(self, loc: torch.Tensor, aux: torch.Tensor, seg_offsets, seg_rows, n_samples: int, seed,
+                               window, threshold=None, windows=False, per_row=True, cum_weights=None, row0=0,
+                               sample0=0) -> dict:
+    """Moving-window totals of the same sample paths, per group of rows (include/bnf.h bnf_predictive_group_windows),
+    without materialising the draws; loc, aux, seg_offsets, seg_rows, row0, sample0 and cum_weights as for
+    `predictive_group_sums`.  TIME is the order of the positions of seg_rows inside a group (`inference.csr_ordered`).
+    The window at a position is the f64 sum of the draws at the last `window` positions up to and including it, clipped
+    at the group's start; an entry of seg_rows outside [0, R) occupies a slot and adds nothing; a NaN draw makes exactly
+    the windows that hold it NaN.  The CANDIDATES are the full-length windows that end at a participating position (for
+    a group shorter than `window`: the whole group, at its last position).  threshold (G,) f64, one per group, compared
+    with strict > (false for NaN).  -> dict of device tensors:
+      'peak' (n_samples, G) f64         the largest candidate window that is not NaN; NaN if there is none
+      'peak_row' (n_samples, G) int32   the table row at which it is first reached, -1 if none
+      'window' (n_samples, R) f64       windows=True: the window, column = POSITION of seg_rows (not table row), at every
+                                        position, candidate or not
+      'count' (n_samples, G) f64        with `threshold`: the candidate windows above it
+      'peak_count' (R,) int32           per_row=True: the paths whose peak window ends at the row
+      'exceed_count' (R,) int32         with `threshold`, per_row=True: the paths whose candidate window ending at the
+                                        row is above it
+    One kernel without a work buffer; a group longer than a tile is finished by one block per path, as in
+    `predictive_group_cumulative` (profiles/group_windows.md).  Deterministic: the same call gives the same bits,
+    whatever n_samples, the cut into calls (sample0) and the outputs asked for."""
+    loc, aux, off, rows, M, R, G = self._group_inputs(loc, aux, seg_offsets, seg_rows)
+    thr = None if threshold is None else self._as_f64(threshold, (G,), 'threshold')
+    n_samples = int(n_samples)
+    out = {'peak': torch.empty((n_samples, G), dtype=torch.float64, device=self.device),
+           'peak_row': torch.empty((n_samples, G), dtype=torch.int32, device=self.device)}
+    if windows:
+      out['window'] = torch.empty((n_samples, R), dtype=torch.float64, device=self.device)
+    if thr is not None:
+      out['count'] = torch.empty((n_samples, G), dtype=torch.float64, device=self.device)
+    if per_row:                             # the library adds to these: zeroed here
+      out['peak_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+      if thr is not None:
+        out['exceed_count'] = torch.zeros((R,), dtype=torch.int32, device=self.device)
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_group_windows(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), G, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), int(window), _ptr(thr),
+        _ptr(out['peak']), _ptr(out['peak_row']), _ptr(out.get('window')), _ptr(out.get('count')),
+        _ptr(out.get('peak_count')), _ptr(out.get('exceed_count'))), 'bnf_predictive_group_windows')
+    torch.cuda.synchronize(self.device)     # `off`, `rows`, `thr` and `cum` are released on return
+    return out
+
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
                         lpd=True, pit=True, weights=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),

@@ -16,6 +16,7 @@ per torchrun rank -- is `distributed.local_shards()`.
 from __future__ import annotations
 
 import contextlib
+import numbers
 import os
 import warnings
 from typing import Any
@@ -757,18 +758,18 @@ def episode_summaries(features, observation_model, params, model_args, num_sampl
     return out
 
 
-def _group_level(level, n_groups):
-  """A (G,) finite level as contiguous float64; None stays None."""
+def _group_level(level, n_groups, name='level'):
+  """A (G,) finite level (or, under another `name`, threshold) as contiguous float64; None stays None."""
   if level is None:
     return None
   try:
     level = np.ascontiguousarray(level, dtype=np.float64)
   except (TypeError, ValueError) as e:
-    raise ValueError(f'level must be an array of numbers of shape ({n_groups},)') from e
+    raise ValueError(f'{name} must be an array of numbers of shape ({n_groups},)') from e
   if level.shape != (n_groups,):
-    raise ValueError(f'level must hold one level per group ({n_groups},); got {level.shape}')
+    raise ValueError(f'{name} must hold one {name} per group ({n_groups},); got {level.shape}')
   if not np.all(np.isfinite(level)):
-    raise ValueError('level must be finite')
+    raise ValueError(f'{name} must be finite')
   return level
 
 
@@ -846,6 +847,102 @@ def cumulative_summaries(features, observation_model, params, model_args, num_sa
       out['crossing_probability'] = cu['cross_count'].cpu().numpy().astype(np.float64) / num_samples
       out['above_probability'] = cu['above_count'].cpu().numpy().astype(np.float64) / num_samples
       out['never'] = (cu['cross_row'] < 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
+    return out
+
+
+def _window_length(window):
+  """The length of a moving window in positions: an integer (not a bool) in [1, 2^31 - 1] -> int."""
+  if isinstance(window, (bool, np.bool_)) or not isinstance(window, numbers.Integral):
+    raise ValueError(f'window must be an integer number of rows; got {window!r}')
+  if not 1 <= int(window) <= 0x7fffffff:
+    raise ValueError(f'window={int(window)}: 1..{0x7fffffff} rows')
+  return int(window)
+
+
+def window_candidates(seg_offsets, seg_rows, n_rows, window):
+  """Per POSITION of seg_rows: does a full-length window end here?  The position takes part (its entry of seg_rows is a
+  table row) and has at least min(window, the group's size) positions of its group up to and including it (include/bnf.h
+  bnf_predictive_group_windows: CANDIDATE) -> (len(seg_rows),) bool."""
+  off = np.asarray(seg_offsets, dtype=np.int64)
+  rows = np.asarray(seg_rows, dtype=np.int64)
+  sizes = np.diff(off)
+  at = np.arange(len(rows), dtype=np.int64) - np.repeat(off[:-1], sizes) + 1      # positions of the group so far
+  return (rows >= 0) & (rows < n_rows) & (at >= np.minimum(int(window), np.repeat(sizes, sizes)))
+
+
+def window_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups, window,
+                     threshold=None, curve=True, observed_peak=None, observed_window=None, observed_count=None,
+                     quantiles=(), compute_dtype=None, weights=None):
+  """Moving-window totals of the joint sample paths, summarised and scored on the GPU: per path and group the total over
+  the last `window` rows at every row in time order, its largest value over the group and the number of windows above
+  the group's threshold are formed without materialising the draws (include/bnf.h bnf_predictive_group_windows); the
+  matrices stay on the device and go through bnf_sample_summaries.  groups = (seg_offsets, seg_rows) with the rows of a
+  group in TIME order (`csr_ordered`); window an integer >= 1; threshold (G,) finite, any sign, compared with strict >;
+  observed_peak / observed_count (G,) and observed_window (n_rows,), per TABLE ROW, the observed values, NaN where not
+  to be scored.  Only FULL-LENGTH windows count (`window_candidates`): a group shorter than `window` has one, the whole
+  group.  -> dict of float64 numpy arrays:
+    'peak_mean' (G,)  'peak_quantiles' (len(quantiles), G)     of the largest window of the group, 'linear' quantiles
+    'peak_crps' (G,)  'peak_pit' (2, G)                        with observed_peak, as `total_summaries` forms them
+    'peak_probability' (n_rows,)      share of the paths whose largest window ends at the row (ties: the earliest)
+  with curve=True, per table row (NaN at a row at which no full-length window ends, so that nobody reads a clipped
+  window as a full one):
+    'window_mean' (n_rows,)  'window_quantiles' (len(quantiles), n_rows)   of the window total ending at the row: the
+                                                               band of the joint paths, which no marginal forecast gives
+    'window_crps' (n_rows,)  'window_pit' (2, n_rows)          with observed_window
+  and with `threshold`:
+    'count_mean', 'count_quantiles', ('count_crps', 'count_pit' with observed_count)   of the number of windows above
+    'exceed_probability' (n_rows,)    share of the paths whose window ending at the row is above the threshold
+    'any' (G,)                        share of the paths with at least one window above (count > 0, formed on the device)
+  The caps of `cumulative_summaries` apply: num_samples <= 16,384 and num_samples * G <= 2^28 cells; curve=True holds the
+  (num_samples, n_rows) windows whole as well: num_samples * n_rows <= 2^28.  ValueError beyond, before any GPU work.
+  A group longer than a tile of 1,024 rows is parallel over the paths only (profiles/group_windows.md).
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = _num_samples(num_samples, 'window totals')
+  levels = _quantile_levels(quantiles)
+  window = _window_length(window)
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  _check_cells(num_samples, n_groups, 'peak matrix is')
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  if curve:
+    _check_cells(num_samples, n_rows, 'window totals are')
+  threshold = _group_level(threshold, n_groups, name='threshold')
+  if threshold is None and observed_count is not None:
+    raise ValueError('observed_count needs a threshold')
+  if not curve and observed_window is not None:
+    raise ValueError('observed_window needs curve=True')
+  observed = {'peak': _per_group('observed_peak', 'value', observed_peak, n_groups),
+              'count': _per_group('observed_count', 'value', observed_count, n_groups)}
+  if observed_window is not None:
+    observed_window = np.ascontiguousarray(observed_window, dtype=np.float64)
+    if observed_window.shape != (n_rows,):
+      raise ValueError(f'observed_window must hold one value per row ({n_rows},); got {observed_window.shape}')
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    wi = eng.predictive_group_windows(loc, aux, seg_offsets, seg_rows, num_samples, seed64, window,
+                                      threshold=threshold, windows=bool(curve), **kw)
+    out = {'peak_probability': wi['peak_count'].cpu().numpy().astype(np.float64) / num_samples}
+    for name in ('peak', 'count') if threshold is not None else ('peak',):
+      y = None if observed[name] is None else torch.from_numpy(observed[name]).to(eng.device)
+      for k, v in eng.sample_summaries(wi[name], y, levels).items():
+        out[f'{name}_{k}'] = v.cpu().numpy()
+    if curve:                                   # column = position: back to table rows through seg_rows
+      pos_rows = np.asarray(seg_rows, dtype=np.int64)
+      full = window_candidates(seg_offsets, seg_rows, n_rows, window)
+      y = None
+      if observed_window is not None:
+        y_pos = np.full(pos_rows.shape, np.nan)
+        y_pos[full] = observed_window[pos_rows[full]]
+        y = torch.from_numpy(y_pos).to(eng.device)
+      for k, v in eng.sample_summaries(wi['window'], y, levels).items():
+        v = v.cpu().numpy()
+        by_row = np.full(v.shape, np.nan)
+        by_row[..., pos_rows[full]] = v[..., full]
+        out[f'window_{k}'] = by_row
+    if threshold is not None:
+      out['exceed_probability'] = wi['exceed_count'].cpu().numpy().astype(np.float64) / num_samples
+      out['any'] = (wi['count'] > 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
     return out
 
 

@@ -356,6 +356,44 @@ def group_target_cumulative(target, seg_offsets, seg_rows, level=None):
   return out
 
 
+def group_target_windows(target, seg_offsets, seg_rows, window, threshold=None):
+  """Observed moving-window totals: per group of a CSR layout whose positions are in time order (`group_rows_ordered`),
+  the float64 sum of `target` (R,) over the last `window` rows at every row at which a FULL-LENGTH window ends (a group
+  shorter than `window` has one: the whole group, at its last row) -> dict:
+    'window' (R,) float64      per TABLE ROW: the window total ending at the row; NaN where no full-length window ends
+                               and where the window holds a NaN target
+    'peak' (G,) float64        the largest window total of the group
+    'peak_row' (G,) int64      the table row at which it is first reached
+  and with `threshold` (G,), one per group, compared with strict >:
+    'count' (G,) float64       the windows of the group above it
+  A group with a NaN target among its rows (and an empty one, which `group_rows` never makes) gives NaN in 'peak' and
+  'count' and -1 in 'peak_row': it is not scored; its windows without a NaN target keep their totals."""
+  target = np.asarray(target, dtype=np.float64)
+  order = np.asarray(seg_rows, dtype=np.int64)
+  offsets = np.asarray(seg_offsets, dtype=np.int64)
+  window = inference._window_length(window)
+  n_groups = len(offsets) - 1
+  out = {'window': np.full(target.shape, np.nan), 'peak': np.full(n_groups, np.nan),
+         'peak_row': np.full(n_groups, -1, dtype=np.int64)}
+  if threshold is not None:
+    threshold = np.asarray(threshold, dtype=np.float64)
+    out['count'] = np.full(n_groups, np.nan)
+  for g in range(n_groups):
+    a, b = offsets[g], offsets[g + 1]
+    if a == b:
+      continue
+    w = min(window, int(b - a))
+    win = np.lib.stride_tricks.sliding_window_view(target[order[a:b]], w).sum(axis=1)   # ends at a + w - 1 .. b - 1
+    out['window'][order[a + w - 1:b]] = win
+    if np.isnan(win).any():                                      # every row lies in some full-length window
+      continue
+    best = int(np.argmax(win))                                   # the first of equal totals
+    out['peak'][g], out['peak_row'][g] = win[best], order[a + w - 1 + best]
+    if threshold is not None:
+      out['count'][g] = float((win > threshold[g]).sum())
+  return out
+
+
 # ---------------------------------------------------------------------------
 # estimators
 # ---------------------------------------------------------------------------
@@ -624,8 +662,8 @@ class BayesianNeuralFieldEstimator:
       'gap', 'iterations', 'converged'   converged: gap <= tol within max_iter updates
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
-    `predict_episodes`, `score_episodes`, `predict_cumulative`, `score_cumulative`, `predict_dependence`,
-    `score_dependence`, `predict_ranking` and `score_ranking`
+    `predict_episodes`, `score_episodes`, `predict_cumulative`, `score_cumulative`, `predict_windows`, `score_windows`,
+    `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking`
     (weights=...) and scored on another table by `weighted_log_density`; they are taken by the marginal forecast as well:
     `predict` and `score` (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.
     `fit` is unchanged."""
@@ -854,30 +892,30 @@ class BayesianNeuralFieldEstimator:
     return res
 
   @staticmethod
-  def _group_level(what, table, level, seg_offsets, seg_rows):
-    """The level of every group from `level`: None, a scalar, a column of `table` or one value per table row; constant
-    within every group and finite, any sign -> (G,) float64 or None."""
+  def _group_level(what, table, level, seg_offsets, seg_rows, name='level'):
+    """The level (or, under another `name`, threshold) of every group from `level`: None, a scalar, a column of `table`
+    or one value per table row; constant within every group and finite, any sign -> (G,) float64 or None."""
     if level is None:
       return None
     if isinstance(level, str):
       if level not in table.columns:
-        raise ValueError(f'{what}: level: {level!r} is not among the columns of the table')
+        raise ValueError(f'{what}: {name}: {level!r} is not among the columns of the table')
       level = table[level].values
     try:
       v = np.asarray(level, dtype=np.float64)
     except (TypeError, ValueError) as e:
-      raise ValueError(f'{what}: level must be a number, a column of the table or one number per row') from e
+      raise ValueError(f'{what}: {name} must be a number, a column of the table or one number per row') from e
     if v.ndim == 0:
       v = np.full(len(table), float(v))
     if v.shape != (len(table),):
-      raise ValueError(f'{what}: level must be a scalar or hold one value per row ({len(table)},); got {v.shape}')
+      raise ValueError(f'{what}: {name} must be a scalar or hold one value per row ({len(table)},); got {v.shape}')
     if not np.all(np.isfinite(v)):
-      raise ValueError(f'{what}: level must be finite')
+      raise ValueError(f'{what}: {name} must be finite')
     ordered = v[np.asarray(seg_rows, dtype=np.int64)]
     starts = np.asarray(seg_offsets[:-1], dtype=np.int64)
     lo, hi = np.minimum.reduceat(ordered, starts), np.maximum.reduceat(ordered, starts)
     if np.any(lo != hi):
-      raise ValueError(f'{what}: level must be constant within every group')
+      raise ValueError(f'{what}: {name} must be constant within every group')
     return lo
 
   def _cumulative_summaries(self, what, table, group_by, level, order_by, quantiles, curve, num_samples, seed, weights,
@@ -972,6 +1010,103 @@ class BayesianNeuralFieldEstimator:
                  crossing_step_crps=out['cross_step_crps'], crossing_step_pit=out['cross_step_pit'],
                  mean_crossing_step_crps=mean(out['cross_step_crps']), crossing_row_probability=prob,
                  mean_crossing_row_probability=mean(prob))
+    return res
+
+  def _window_summaries(self, what, table, group_by, window, threshold, order_by, quantiles, curve, num_samples, seed,
+                        weights, target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='window totals', target=target,
+                    ordered=True, order_by=order_by)
+    try:
+      window = inference._window_length(window)
+    except ValueError as e:
+      raise ValueError(f'{what}: {e}') from None
+    thr = self._group_level(what, table, threshold, f.seg_offsets, f.seg_rows, name='threshold')
+    for n, held in ((len(f.keys), 'groups: the peak matrix is'), (len(table) if curve else 0, 'rows: the window totals are')):
+      if int(num_samples) * n > inference._TOTALS_MAX_CELLS:             # before the host pass over the observed windows
+        raise ValueError(f'{what}: {num_samples} sample paths x {n} {held} held whole on the device, at most '
+                         f'{inference._TOTALS_MAX_CELLS} cells')
+    observed = None if f.y is None else group_target_windows(f.y, f.seg_offsets, f.seg_rows, window, thr)
+    obs_kw = {}
+    if observed is not None:
+      obs_kw['observed_peak'] = observed['peak']
+      if curve:
+        obs_kw['observed_window'] = observed['window']
+      if thr is not None:
+        obs_kw['observed_count'] = observed['count']
+    out = f.run(inference.window_summaries, window=window, threshold=thr, curve=bool(curve), quantiles=tuple(quantiles),
+                **obs_kw)
+    res = {'keys': f.keys, 'peak_mean': out['peak_mean'], 'peak_quantiles': out['peak_quantiles'],
+           'peak_probability': out['peak_probability']}
+    if curve:
+      res.update(window_mean=out['window_mean'], window_quantiles=out['window_quantiles'])
+    if thr is not None:
+      res.update(count_mean=out['count_mean'], count_quantiles=out['count_quantiles'],
+                 exceed_probability=out['exceed_probability'], any=out['any'])
+    return res, out, observed
+
+  def predict_windows(self, table, group_by, window, threshold=None, order_by=None, quantiles=(0.5,), curve=True,
+                      num_samples=1000, seed=0, weights=None):
+    """Moving-window totals of the sample paths of `predict_samples(table, num_samples, seed)`: the total over the last
+    `window` rows of a group at every row (7-day incidence from daily rows), the worst `window` rows of the group and
+    how often a window total passes a limit, formed and summarised on the GPU (neither the draws nor the matrices leave
+    the device).  A window total is not a difference of two marginal bands: its band, its peak and the probability that
+    it passes a limit need the joint paths.  These depend on the ORDER of a group's rows: `order_by=None` orders them by
+    the time column (feature_cols[0]), a column name by that column; ties keep table order.  window: an integer number
+    of rows >= 1.  Only FULL-LENGTH windows count; a group with fewer rows than `window` has one, its total.
+    threshold: a scalar, a column name or one value per row, constant within every group and finite (any sign), in the
+    units of the target column, compared with strict >.  -> dict:
+      'keys'                     the groups, as in `predict_samples`
+      'peak_mean' (G,)  'peak_quantiles' (len(quantiles), G)   the largest window total of the group
+      'peak_probability' (len(table),)   the share of the paths whose largest window ends at the row (ties, frequent for
+                                 counts, go to the earliest row): sums to 1 over the rows of every group
+    with curve=True (holds num_samples x len(table) values on the device, at most 2^28):
+      'window_mean' (len(table),)  'window_quantiles' (len(quantiles), len(table))   the window total ending at the row;
+                                 NaN at the first window - 1 rows of a group, at which no full-length window ends
+    and with `threshold`:
+      'count_mean' (G,)  'count_quantiles' (len(quantiles), G)   the number of windows of the group above the threshold
+      'exceed_probability' (len(table),)   the share of the paths whose window ending at the row is above it
+      'any' (G,)                 the share of the paths with at least one window above it
+    num_samples <= 16,384.  A group of more than 1,024 rows is worked on by one workgroup per path
+    (profiles/group_windows.md).  weights: member weights of the sample paths as in `predict_samples`; None: equal
+    weights."""
+    return self._window_summaries('predict_windows', table, group_by, window, threshold, order_by, quantiles, curve,
+                                  num_samples, seed, weights)[0]
+
+  def score_windows(self, table, group_by, window, threshold=None, order_by=None, quantiles=(0.025, 0.5, 0.975),
+                    curve=True, num_samples=1000, seed=0, weights=None):
+    """The forecast of `predict_windows` scored against the window totals observed in `table[target_col]`, on the GPU.
+    -> the dict of `predict_windows` plus
+      'observed_peak' (G,)  'observed_peak_row' (G,)   `group_target_windows` on the target; NaN / -1 when any row of the
+                                 group has a NaN target: such a group is not scored
+      'peak_crps' (G,)  'peak_pit' (2, G)   ensemble CRPS and the share of the sampled peaks <= and < the observed one;
+                                 NaN where not scored
+      'peak_row_probability' (G,)   the forecast probability ('peak_probability') of the observed peak row
+      'n'                        number of groups scored       'mean_peak_crps', 'mean_peak_row_probability'  means over them
+    with curve=True:
+      'observed_window' (len(table),)   the observed window total ending at the row; NaN where no full-length window
+                                 ends or the window holds a NaN target
+      'window_crps' (len(table),)  'window_pit' (2, len(table))   the same scores row by row; NaN where not scored
+      'mean_window_crps'         mean over the scored rows
+    and with `threshold`:
+      'observed_count' (G,)      the observed windows of the group above the threshold
+      'count_crps' (G,)  'count_pit' (2, G)  'mean_count_crps'
+    The target checks are those of `score_totals`."""
+    res, out, observed = self._window_summaries('score_windows', table, group_by, window, threshold, order_by, quantiles,
+                                                curve, num_samples, seed, weights, target=True)
+    scored = ~np.isnan(observed['peak'])
+    mean = lambda a: float(np.mean(a[scored], dtype=np.float64)) if scored.any() else float('nan')
+    row = observed['peak_row']
+    prob = np.where(scored, res['peak_probability'][np.maximum(row, 0)], np.nan)
+    res.update(observed_peak=observed['peak'], observed_peak_row=row, peak_crps=out['peak_crps'],
+               peak_pit=out['peak_pit'], peak_row_probability=prob, n=int(scored.sum()),
+               mean_peak_crps=mean(out['peak_crps']), mean_peak_row_probability=mean(prob))
+    if curve:
+      rows = ~np.isnan(observed['window'])
+      res.update(observed_window=observed['window'], window_crps=out['window_crps'], window_pit=out['window_pit'],
+                 mean_window_crps=float(np.mean(out['window_crps'][rows], dtype=np.float64)) if rows.any() else float('nan'))
+    if 'count' in observed:
+      res.update(observed_count=observed['count'], count_crps=out['count_crps'], count_pit=out['count_pit'],
+                 mean_count_crps=mean(out['count_crps']))
     return res
 
   def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=False, p=0.5,

@@ -437,6 +437,59 @@ int bnf_predictive_group_cumulative(bnf_handle* h, const float* loc, const float
                                     double* out_running, double* out_cross_step, int32_t* out_cross_row,
                                     uint32_t* cross_count, uint32_t* above_count);
 
+/* MOVING-WINDOW TOTALS of the same sample paths, per group of rows: the total over the last w positions at every
+ * position, its peak over the group and how often it lies above a limit, without materialising the draws (the reference
+ * has no counterpart).  loc, aux, seg_offsets, seg_rows, row0, sample0 and cum_weights (NULL = equal weights) as for
+ * bnf_predictive_group_cumulative.  TIME is the order of the positions of seg_rows inside a group
+ * (inference.csr_ordered).  window is an int32 w >= 1, one per call.  Group g has the positions o0 .. o1 - 1, and p is
+ * one of them:
+ *   DRAW.  x[s][p] is the f32 that bnf_predictive_samples writes for (seed, sample0 + s, row0 + row), bit for bit,
+ *     widened to f64.
+ *   ENTRIES THAT TAKE NO PART.  An entry of seg_rows outside [0, n_rows) takes no part.  It occupies a slot of the
+ *     window, because windows are counted in positions.  It adds nothing, is never NaN and is never a candidate.
+ *   WINDOW SUM.  win[s][p] is the f64 sum of the draws at the participating positions in max(o0, p - w + 1) .. p.  The
+ *     window is clipped at the group's start.
+ *   NaN DRAWS.  A NaN draw makes exactly the windows that contain it NaN.  The window ending w positions later is finite
+ *     again.  This is deliberately not the behaviour of a naive sliding sum, which stays NaN for ever.
+ *   CANDIDATE.  Position p is a candidate if it takes part and p - o0 + 1 >= min(w, o1 - o0).  These are the full-length
+ *     windows.  For a group shorter than w, the candidate is the one window that is the whole group, which ends at its
+ *     last position.  With w >= the group's size, the only candidate window is therefore the group total.
+ *   PEAK.  peak[s][g] is the largest non-NaN win over the candidates of g; peak_row is the TABLE ROW of the earliest
+ *     position at which it is reached.  With no candidate, or none that is not NaN, the results are NaN and -1.  The
+ *     total order is that of bnf_predictive_group_extremes: value descending, position ascending, NaN entering as -inf.
+ *   THRESHOLD.  threshold DEVICE (n_groups,) f64 or NULL, one limit per group, like `level`.  The test is
+ *     win > threshold[g]: strict, in f64, false for NaN.  With a threshold:
+ *       count[s][g] is the number of candidates above it, as an f64;
+ *       exceed_count[r] += the paths whose candidate window ending at r's position is above it.
+ * Outputs, each skipped when its pointer is NULL except out_peak:
+ *   out_peak DEVICE (n_samples, n_groups) f64, required
+ *   out_peak_row DEVICE (n_samples, n_groups) int32
+ *   out_window DEVICE (n_samples, n_rows) f64: win, column = POSITION of seg_rows (not table row); written at every
+ *     position, candidate or not (the clipped sum)
+ *   out_count DEVICE (n_samples, n_groups) f64, needs threshold
+ *   peak_count DEVICE (n_rows,) uint32, ZEROED BY THE CALLER: += the paths whose peak window ends at r
+ *   exceed_count DEVICE (n_rows,) uint32, ZEROED BY THE CALLER, needs threshold
+ * A group without a candidate reports peak NaN, peak_row -1, count 0.
+ * One kernel over tiles of BNF_GROUP_TILE positions, no work buffer: what is summed from a group's start is
+ * x[p] - x[p - w]; the draw that leaves comes from the draws of the block's current and previous tile kept in LDS, or,
+ * further back, is drawn again: a position costs one draw for w <= BNF_GROUP_TILE and at most two beyond
+ * (bnf_windows.h).  A group that leaves its tile through the far edge is finished by the block of the tile it starts in;
+ * no workgroup waits for another.  A long group is therefore parallel over the samples only.  Draws are taken to be
+ * finite or NaN.
+ * DETERMINISM: no floating-point atomics; two calls give the same bits.  The bits of every output depend only on the
+ * seed, sample0 + s, row0, loc, aux, cum_weights, window, threshold and the CSR arrays: not on n_samples, on how the
+ * samples are cut into calls, on the launch geometry or on which output pointers are NULL.  They may depend on where a
+ * group lies on the position axis: the order of the f64 additions follows the tiling.  For NB and ZINB everything is an
+ * exact integer below 2^53, so the order plays no part.
+ * BNF_ERR_INVALID, with nothing written, for a NULL out_peak, for window < 1, for out_count or exceed_count non-NULL
+ * while threshold is NULL, and for n_members, n_rows, n_groups or n_samples < 1.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+int bnf_predictive_group_windows(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                 const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
+                                 uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights, int32_t window,
+                                 const double* threshold, double* out_peak, int32_t* out_peak_row, double* out_window,
+                                 double* out_count, uint32_t* peak_count, uint32_t* exceed_count);
+
 /* SCORES of held-out observations y against the ensemble: what a user of the reference computes on the host from
  * `likelihood_model()` (`.log_prob`, `.cdf`; spatiotemporal.py:433-468) plus the scores of the equal-weight mixture over
  * members.  loc, aux as for bnf_predictive_samples, with the same per-member laws (observation model of the handle);
