@@ -323,7 +323,7 @@ def test_forward_only_and_quantiles():
   loc, aux = eng.forward(th_d, X_d)          # 3 member chunks x 3 row chunks
   torch.cuda.synchronize()
   mu_o, sd_o = O.predict_normal(model, theta, X)
-  assert util.rel_err(loc.cpu().numpy(), mu_o) < 2e-4
+  assert util.rel_err(loc.cpu().numpy(), mu_o) < G['out']
   np.testing.assert_allclose(aux[:, 0].cpu().numpy(), sd_o, rtol=1e-5)
   qs = (0.5, 0.025, 0.975)
   q_d = eng.normal_mixture_quantiles(loc, aux[:, 0], qs).cpu().numpy()
