@@ -1,0 +1,381 @@
+"""The optimiser state and the gradient buffer, held after every call of `train`.
+
+Every other gradient assertion of the suite goes through `debug_loss_and_grad`, which runs the step with apply = false:
+k_adam_map / k_vi_adam then neither update m, v, theta nor clear the gradient buffer, the "keep" ranges (the gradient
+entries the NEXT step's weight-gradient kernel stores instead of accumulating, which the optimiser therefore does not
+clear) are never in force, and the call ends by clearing the whole buffer itself.  Here the production step is the subject.
+Two handles per case, built with identical arguments: the ENGINE (only init_params / set_params and train are called on
+it) and the PROBE (only set_params and debug_loss_and_grad), whose gradient path the rest of the suite holds to the float64
+oracle.  Same kernels, same operands: the two sides differ by the order of the f32 atomics and nothing else, so no
+comparison below carries a dtype bar.  `Engine.state` and `Engine.params` are read as the device tensors they are.
+
+(a) frozen run, learning_rate = 0: the parameters never move, so the state after K steps is a closed form in the probe's
+    gradients at theta0 (tests/optimizer_ref.py `moments`) -- also with minibatches and in VI, where every step draws
+    other rows / other noise.  Two calls of `train`, so the step count carries over.  A gradient entry that is not cleared,
+    cleared but stored over, or kept although the next step accumulates, is an error of order 1 of its leaf's max.
+(b) moving run, learning_rate = 0.005, four calls train(t, 1): m and v from the engine's own previous state and the
+    probe's gradient at the engine's theta_t (its f32 bits); theta_{t+1} from the engine's own m_{t+1}, v_{t+1} -- pure
+    arithmetic, bar: one f32 ulp of theta + 2e-6 |update| (hardware rcp and sqrt at 1 ulp each, a handful of f32
+    roundings, the f32 bias corrections).  A step count off by one moves the update by tens of percent at t = 2.
+(c) the debug path leaves training alone: twin engines, one with debug_loss_and_grad between its steps.
+(d) BNF_GRAPH=1 at the one geometry the suite replays (fp32, W 64, depth 2, full batch): the bias corrections and the loss
+    column come from device memory.  Other pipelines under capture are not covered.
+
+THE PLANS (wgrad_plan in bnf_api.hip, read for every layer of every case; 3 members, VI: 3 x S virtual members; the
+default problem has F = 49 features, Fp = 64; K = the padded batch Bp: a multiple of 128, of 256 in the panel pipeline;
+split-K = max(1, (Bp / 32 or 64) / 4) for the 128 x 128 kernel).  "1": the kernel stores, the range may be kept; "> 1":
+f32 atomics into a buffer the optimiser must have cleared.
+   1  MAP fp32 / fp32_split, layers / auto, W 64, depth 2   100 rows: Bp 128, L0 TN128 x1, L1 TN128 x1 (L1 kept)
+                                                            200 rows: Bp 256, L0 TN128 x2, L1 TN128 x2 (nothing kept)
+   2  MAP fp32 auto W 256 depth 3, 100 rows                 Bp 128, L0 / L1 / L2 TN128 x1 (L1 kept, L2 cleared and stored)
+   3  MAP fp32 auto W 100 (run at 128) depth 2, 100 rows    Bp 128, TN128 x1 x1, padded: nothing kept, gradf folded
+   4  MAP bf16 layers W 128 depth 2                         300 rows: Bp 384, TN128 x1 x1;  600 rows: Bp 640, TN128 x2 x2
+   5  MAP bf16 panel W 256 depth 2                          200 rows: Bp 256, TN128 x1 x1;  600 rows: Bp 768, TN128 x3 x3
+      MAP bf16 panel W 512 depth 2                          200 rows: L0 SKINNY x1, L1 TN128 x1;  600 rows: SKINNY x3, TN128 x3
+   6  MAP bf16 panel BNF_BIG_TILES=2 W 256 depth 3, 300 rows   Bp 512, L0 TN128 x2, L1 + L2 RING x1 in one launch (L1 kept)
+   7  MAP fp8 panel W 256 depth 2                           200 rows: fp8 TN128 x1 x1;  600 rows: x3 x3
+   8  MAP fp32 auto W 64, 333 rows in batches of 100        Bp 128, TN128 x1 x1 (L1 kept), 3 steps per epoch
+      MAP bf16 panel W 256, 1500 rows in batches of 600     Bp 768, TN128 x3 x3, 2 steps per epoch
+   9  MAP NB / ZINB fp32 auto W 64, 200 rows                Bp 256, TN128 x2 x2
+  10  MAP prior_weight 0 fp32 auto W 64, 100 rows           Bp 128, TN128 x1 x1 (L1 kept)
+  11  VI S 3 fp32 W 64 depth 2                              100 rows: TN128 x1 x1 (L0 kept with F * W, L1 kept);  200 rows: x2 x2
+  12  VI S 3 bf16 panel W 256 depth 2                       300 rows: Bp 512, TN128 x2 x2;  200 rows: Bp 256, x1 x1 (both kept)
+  13  VI S 3 bf16 panel BNF_VI_KEEP_Z=1 W 256, 300 rows     Bp 512, TN128 x2 x2
+  14  VI S 2 fp32 W 64 depth 1, 200 rows in batches of 64   Bp 128, L0 TN128 x1 (kept)
+The panel pipeline pads the batch to 256 rows, so its stored plan ends at 256 rows, not at 384: cases 5 and 7 run 200 rows
+where the issue's table says 300 (Bp 512: split-K 2, the same side as 600), and case 12 runs 200 rows as well.
+
+THE BARS for the moments.  Measured first on the probe alone: two debug_loss_and_grad calls at the same parameters, per
+leaf relative to the leaf's max (`probe_spread`, asserted again by test_probe_spread...).  bar(g) = max(1e-4, 3 x the worst
+spread measured), capped at 1e-2; 1e-4 is the project's bar for two evaluations of one step
+(test_panel_repeated_step_is_reproducible, FP32_GATE['grad']).  m takes it against the expected m, v twice it.  The measured
+spreads are in SPREAD below, per case.  No element, leaf or member is left out of any comparison.
+Measured against these bars on the real build: every moment within 5.5e-7 of its leaf's max (worst: the twin engines on the
+panel), every update within 0.50 of its tolerance (the rounding of the final subtraction).
+"""
+import numpy as np
+import pytest
+import torch
+
+from tests import optimizer_ref as R
+from tests import util
+
+pytestmark = pytest.mark.gpu
+
+E, SEED, MEMBER_OFFSET, LR = 3, 7, 5, 0.005
+LOSS_RTOL = 1e-5          # two evaluations of one step's loss (test_results_do_not_depend_on_stale_lds)
+BAR_FLOOR, BAR_CAP = 1e-4, 1e-2
+
+
+def _case(mode='map', dtype='fp32', pipeline='auto', width=64, depth=2, rows=100, batch=None, env=(), obs='NORMAL',
+          prior_weight=1.0, S=3, moving=False):
+  name = '-'.join([mode, dtype, pipeline, f'w{width}', f'd{depth}', f'r{rows}'] + ([f'b{batch}'] if batch else []) +
+                  ([obs] if obs != 'NORMAL' else []) + (['pw0'] if prior_weight == 0 else []) +
+                  ([f's{S}'] if mode == 'vi' else []) + [f'{k}={v}' for k, v in env])
+  return dict(name=name, mode=mode, dtype=dtype, pipeline=pipeline, width=width, depth=depth, rows=rows, batch=batch,
+              env=tuple(env), obs=obs, prior_weight=prior_weight, S=S, moving=moving)
+
+
+CASES = (
+    # 1
+    [_case(dtype=d, pipeline=p, rows=r, moving=True) for d in ('fp32', 'fp32_split') for p in ('layers', 'auto')
+     for r in (100, 200)] +
+    [_case(width=256, depth=3, moving=True),                                                    # 2
+     _case(width=100, moving=True),                                                             # 3
+     _case(dtype='bf16', pipeline='layers', width=128, rows=300),                               # 4
+     _case(dtype='bf16', pipeline='layers', width=128, rows=600),
+     _case(dtype='bf16', pipeline='panel', width=256, rows=200, moving=True),                   # 5
+     _case(dtype='bf16', pipeline='panel', width=256, rows=600, moving=True),
+     _case(dtype='bf16', pipeline='panel', width=512, rows=200),
+     _case(dtype='bf16', pipeline='panel', width=512, rows=600),
+     _case(dtype='bf16', pipeline='panel', width=256, depth=3, rows=300, env=(('BNF_BIG_TILES', '2'),)),   # 6
+     _case(dtype='fp8', pipeline='panel', width=256, rows=200, moving=True),                    # 7
+     _case(dtype='fp8', pipeline='panel', width=256, rows=600, moving=True),
+     _case(rows=333, batch=100),                                                                # 8
+     _case(dtype='bf16', pipeline='panel', width=256, rows=1500, batch=600),
+     _case(rows=200, obs='NB'), _case(rows=200, obs='ZINB'),                                    # 9
+     _case(prior_weight=0.0),                                                                   # 10
+     _case(mode='vi', rows=100, moving=True), _case(mode='vi', rows=200, moving=True),          # 11
+     _case(mode='vi', dtype='bf16', pipeline='panel', width=256, rows=300, moving=True),        # 12
+     _case(mode='vi', dtype='bf16', pipeline='panel', width=256, rows=200),
+     _case(mode='vi', dtype='bf16', pipeline='panel', width=256, rows=300, env=(('BNF_VI_KEEP_Z', '1'),)),   # 13
+     _case(mode='vi', depth=1, rows=200, batch=64, S=2)])                                       # 14
+MOVING = [c for c in CASES if c['moving']]
+_ids = lambda cases: [c['name'] for c in cases]
+
+# Worst leaf of |g' - g| / max |g| over four evaluations of the probe at the same parameters, per case (see THE BARS), as
+# measured on an MI355X.  Exactly 0 wherever no output has more than two atomic addends (every split-K = 1 plan, and the
+# f32-class split-K = 2 plans at these row counts: two addends commute); at most 3.2e-7 otherwise, so every bar below is
+# the floor, 1e-4 -- three hundred times the worst spread.
+SPREAD = {
+    'map-fp32-layers-w64-d2-r100': 0.0, 'map-fp32-layers-w64-d2-r200': 0.0,
+    'map-fp32-auto-w64-d2-r100': 0.0, 'map-fp32-auto-w64-d2-r200': 0.0,
+    'map-fp32_split-layers-w64-d2-r100': 0.0, 'map-fp32_split-layers-w64-d2-r200': 3.0e-8,
+    'map-fp32_split-auto-w64-d2-r100': 0.0, 'map-fp32_split-auto-w64-d2-r200': 0.0,
+    'map-fp32-auto-w256-d3-r100': 0.0, 'map-fp32-auto-w100-d2-r100': 0.0,
+    'map-bf16-layers-w128-d2-r300': 7.9e-8, 'map-bf16-layers-w128-d2-r600': 1.2e-7,
+    'map-bf16-panel-w256-d2-r200': 0.0, 'map-bf16-panel-w256-d2-r600': 1.6e-7,
+    'map-bf16-panel-w512-d2-r200': 0.0, 'map-bf16-panel-w512-d2-r600': 1.8e-7,
+    'map-bf16-panel-w256-d3-r300-BNF_BIG_TILES=2': 2.6e-7,
+    'map-fp8-panel-w256-d2-r200': 0.0, 'map-fp8-panel-w256-d2-r600': 1.9e-7,
+    'map-fp32-auto-w64-d2-r333-b100': 0.0, 'map-bf16-panel-w256-d2-r1500-b600': 1.5e-7,
+    'map-fp32-auto-w64-d2-r200-NB': 0.0, 'map-fp32-auto-w64-d2-r200-ZINB': 0.0,
+    'map-fp32-auto-w64-d2-r100-pw0': 0.0,
+    'vi-fp32-auto-w64-d2-r100-s3': 0.0, 'vi-fp32-auto-w64-d2-r200-s3': 0.0,
+    'vi-bf16-panel-w256-d2-r300-s3': 3.2e-7, 'vi-bf16-panel-w256-d2-r200-s3': 0.0,
+    'vi-bf16-panel-w256-d2-r300-s3-BNF_VI_KEEP_Z=1': 3.2e-7,
+    'vi-fp32-auto-w64-d1-r200-b64-s2': 0.0,
+}
+
+
+def _bar(case):
+  return min(BAR_CAP, max(BAR_FLOOR, 3 * SPREAD[case['name']]))
+
+
+def _problem(case):
+  return util.make_problem(n_rows=case['rows'], width=case['width'], depth=case['depth'], observation_model=case['obs'])
+
+
+def _handle(case, problem, monkeypatch, learning_rate=LR, env=()):
+  from bayesnf_amd.engine import Engine
+  for k, v in tuple(case['env']) + tuple(env):
+    monkeypatch.setenv(k, v)        # read at bnf_create
+  net, _, X, y = problem
+  kw = dict(mode='vi', vi_samples=case['S'], kl_weight=0.2) if case['mode'] == 'vi' else dict(prior_weight=case['prior_weight'])
+  return Engine(net, X=X, y=y, members=E, seed=SEED, member_offset=MEMBER_OFFSET, batch=case['batch'],
+                learning_rate=learning_rate, compute_dtype=case['dtype'], pipeline=case['pipeline'], **kw)
+
+
+def _init(eng, problem):
+  """The estimators' own start; returns the parameters as the engine holds them (f32 bits)."""
+  y = problem[3]
+  eng.init_params(float(np.log(np.nanstd(y) / 2)) if eng.mode == 'map' else 0.0)
+  return eng.get_params().copy()
+
+
+def _state(eng):
+  """The handle's optimiser state -> (2 or 4, E, P) f32: MAP m, v; VI m_mu, v_mu, m_rho, v_rho."""
+  torch.cuda.synchronize()
+  s = eng.state.detach().cpu().numpy()
+  k = 4 if eng.mode == 'vi' else 2
+  assert s.size == k * eng.members * eng.net.P, (s.size, k, eng.members, eng.net.P)
+  return s.reshape(k, eng.members, eng.net.P).copy()
+
+
+def _grad_blocks(g):
+  """The probe's gradients in the order of the state's (m, v) pairs: MAP (E, P) -> [g]; VI (2, E, P) -> [g_mu, g_rho]."""
+  return [g] if g.ndim == 2 else [g[0], g[1]]
+
+
+def _assert_live(case, model, g):
+  """The probe's gradient is not trivially zero (an all-zero gradient would meet an all-zero state): every leaf of every
+  member has a nonzero entry, but for the leaves that are zero by construction -- MAP at the initial values: the
+  inflation leaf (no likelihood term unless ZINB, prior gradient tanh(0)); prior_weight 0: the shape leaf as well."""
+  zero_ok = set()
+  if case['mode'] == 'map':
+    if case['obs'] != 'ZINB':
+      zero_ok.add('inflated_loc_probs')
+    if case['prior_weight'] == 0:
+      zero_ok.add('shape')
+  for block in _grad_blocks(g):
+    assert np.all(np.isfinite(block)), case['name']
+    dead = [lf.name for lf in model.leaves if lf.name not in zero_ok
+            and not np.all(np.max(np.abs(block[:, lf.offset:lf.offset + lf.size]), axis=1) > 0)]
+    assert not dead, (case['name'], dead)
+
+
+def _check_state(model, state, want_pairs, bar, what):
+  """state (2k, E, P) against k pairs (m, v): m at `bar`, v at twice it, every leaf of every member."""
+  bad = {}
+  for i, (m, v) in enumerate(want_pairs):
+    for name, got, want, b in (('m', state[2 * i], m, bar), ('v', state[2 * i + 1], v, 2 * bar)):
+      f = R.leaf_failures(model, got, want, b)
+      if f:
+        bad[f'{name}[{i}]'] = f
+  assert not bad, (what, bar, bad)
+
+
+def _steps(case):
+  """The calls (epoch0, num_epochs) of the frozen run and the probe's (epoch, step) arguments of every optimiser step."""
+  if case['mode'] == 'vi':            # one step per "epoch"; debug_loss_and_grad takes the step as `step`
+    return [(0, 2), (2, 3)], [[(0, t)] for t in range(5)]
+  if case['batch']:
+    spe = case['rows'] // case['batch']
+    return [(0, 1), (1, 1)], [[(ep, s) for s in range(spe)] for ep in range(2)]
+  return [(0, 2), (2, 3)], [[(ep, 0)] for ep in range(5)]
+
+
+def probe_spread(case, problem, monkeypatch, repeats=3):
+  """Worst leaf of max |g' - g| / max |g| between evaluations of the probe at the same parameters and step."""
+  probe = _handle(case, problem, monkeypatch)
+  _init(probe, problem)
+  _, g0 = probe.debug_loss_and_grad(0, 0)
+  worst = 0.0
+  for _ in range(repeats - 1):
+    _, g = probe.debug_loss_and_grad(0, 0)
+    for a, b in zip(_grad_blocks(g), _grad_blocks(g0)):
+      worst = max(worst, max(v[0] for v in R.leaf_report(problem[1], a, b).values()))
+  probe.close()
+  return worst
+
+
+@pytest.mark.parametrize('case', CASES, ids=_ids(CASES))
+def test_probe_spread_is_within_a_third_of_the_bar(case, monkeypatch):
+  """What the bars stand on: two evaluations of one step differ by the order of the f32 atomics only."""
+  problem = _problem(case)
+  spread = probe_spread(case, problem, monkeypatch)
+  print(f'[spread] {case["name"]}: {spread:.3e}')
+  assert 3 * spread <= _bar(case), (spread, _bar(case))
+
+
+@pytest.mark.parametrize('case', CASES, ids=_ids(CASES))
+def test_frozen_run_state_is_the_closed_form_of_the_probe_gradients(case, monkeypatch):
+  """(a)"""
+  problem = _problem(case)
+  model = problem[1]
+  eng = _handle(case, problem, monkeypatch, learning_rate=0.0)
+  probe = _handle(case, problem, monkeypatch, learning_rate=0.0)
+  theta0 = _init(eng, problem)
+  probe.set_params(theta0)
+  calls, steps = _steps(case)
+  losses = [eng.train(e0, n) for e0, n in calls]
+  torch.cuda.synchronize()
+  losses = np.concatenate([l.cpu().numpy() for l in losses], axis=1)
+  state, theta = _state(eng), eng.get_params()
+  grads, want_loss = [], []
+  for column in steps:
+    out = [probe.debug_loss_and_grad(ep, s) for ep, s in column]
+    grads += [g for _, g in out]
+    want_loss.append(np.mean([l.astype(np.float64) for l, _ in out], axis=0))   # the column is the mean over its steps
+  eng.close(); probe.close()
+  np.testing.assert_array_equal(theta, theta0)                  # bit for bit: also no NaN out of the update
+  for g in grads:
+    _assert_live(case, model, g)
+  k = len(_grad_blocks(grads[0]))
+  want = [R.moments([_grad_blocks(g)[i] for g in grads]) for i in range(k)]
+  _check_state(model, state, want, _bar(case), case['name'])
+  np.testing.assert_allclose(losses, np.stack(want_loss, axis=1), rtol=LOSS_RTOL)
+
+
+def _check_update(model, theta, new_theta, m, v, t, what):
+  """theta_{t} from theta_{t-1} and the engine's own moments after step t: |error| <= one f32 ulp of theta + 2e-6 |update|.
+  The learning rate is the f32 the ABI carries."""
+  want = R.theta_next(theta, m, v, t, float(np.float32(LR)))
+  ulp = np.spacing(np.maximum(np.abs(theta), np.abs(new_theta)).astype(np.float32)).astype(np.float64)
+  tol = ulp + 2e-6 * np.abs(want - theta.astype(np.float64))
+  err = np.abs(new_theta.astype(np.float64) - want)
+  err = np.where(np.isnan(err), np.inf, err)
+  if np.all(err <= tol):
+    return
+  e, p = np.unravel_index(int(np.argmax(err / tol)), err.shape)
+  leaf = next(lf for lf in model.leaves if lf.offset <= p < lf.offset + lf.size)
+  raise AssertionError((what, f'step {t}', leaf.name, int(e), int(p - leaf.offset), float(err[e, p]), float(tol[e, p]),
+                        float(want[e, p] - theta[e, p]), int(np.sum(err > tol))))
+
+
+@pytest.mark.parametrize('case', MOVING, ids=_ids(MOVING))
+def test_moving_run_follows_the_probe_gradient_at_every_step(case, monkeypatch):
+  """(b)"""
+  problem = _problem(case)
+  model = problem[1]
+  eng = _handle(case, problem, monkeypatch)
+  probe = _handle(case, problem, monkeypatch)
+  theta = _init(eng, problem)
+  state = np.zeros_like(_state(eng))                           # init_params clears the state
+  np.testing.assert_array_equal(_state(eng), state)
+  for t in range(4):
+    probe.set_params(theta)
+    loss_p, g = probe.debug_loss_and_grad(*((0, t) if case['mode'] == 'vi' else (t, 0)))
+    loss = eng.train(t, 1)
+    new_state, new_theta = _state(eng), eng.get_params().copy()
+    if t == 0:
+      _assert_live(case, model, g)
+    blocks = _grad_blocks(g)
+    want = [R.moments_next(state[2 * i], state[2 * i + 1], blocks[i]) for i in range(len(blocks))]
+    _check_state(model, new_state, want, _bar(case), (case['name'], f'step {t + 1}'))
+    th, nth = (theta, new_theta) if case['mode'] == 'vi' else (theta[None], new_theta[None])
+    for i, what in enumerate(('mu', 'rho') if case['mode'] == 'vi' else ('theta',)):
+      _check_update(model, th[i], nth[i], new_state[2 * i], new_state[2 * i + 1], t + 1, (case['name'], what))
+    np.testing.assert_allclose(loss.cpu().numpy()[:, 0], loss_p, rtol=LOSS_RTOL)
+    state, theta = new_state, new_theta
+  eng.close(); probe.close()
+
+
+# stored + kept range, atomics + cleared range, the panel pipeline (the bars are those of the same cases above)
+TWINS = [_case(rows=100), _case(rows=200), _case(dtype='bf16', pipeline='panel', width=256, rows=600)]
+
+
+@pytest.mark.parametrize('case', TWINS, ids=_ids(TWINS))
+def test_debug_path_leaves_training_alone(case, monkeypatch):
+  """(c) Twin engines from the same generic parameters (util.random_theta: every leaf of order 1, so three steps of
+  lr move no leaf by more than a percent of its max and the two trajectories stay comparable at the moment bars); one has
+  debug_loss_and_grad called before and between its single-step train calls.  Then init_params: the state is all zero and
+  the next step's m is 0.1 g again (the step count starts over)."""
+  problem = _problem(case)
+  model = problem[1]
+  a = _handle(case, problem, monkeypatch)
+  b = _handle(case, problem, monkeypatch)
+  theta0 = util.random_theta(model, E, seed=3, scale=0.3).astype(np.float32)
+  for eng in (a, b):
+    _init(eng, problem)                                         # clears the state
+    eng.set_params(theta0)
+  for t in range(3):
+    b.debug_loss_and_grad(t, 0)
+    la, lb = a.train(t, 1), b.train(t, 1)
+    torch.cuda.synchronize()
+    np.testing.assert_allclose(lb.cpu().numpy(), la.cpu().numpy(), rtol=LOSS_RTOL)
+  b.debug_loss_and_grad(3, 0)
+  bar = _bar(case)
+  sa, sb = _state(a), _state(b)
+  _check_state(model, sb, [(sa[0], sa[1])], bar, (case['name'], 'twin state'))
+  bad = R.leaf_failures(model, b.get_params(), a.get_params(), bar)
+  assert not bad, (case['name'], 'twin parameters', bad)
+  theta_i = _init(b, problem)
+  np.testing.assert_array_equal(_state(b), np.zeros_like(sb))
+  a.set_params(theta_i)                                         # the clean twin is the probe now
+  _, g = a.debug_loss_and_grad(0, 0)
+  b.train(0, 1)
+  _check_state(model, _state(b), [R.moments([g])], bar, (case['name'], 'first step after init_params'))
+  _check_update(model, theta_i, b.get_params(), *_state(b), 1, (case['name'], 'first step after init_params'))
+  a.close(); b.close()
+
+
+GRAPH = _case(rows=200)
+
+
+def test_graph_replay_frozen_run_is_the_closed_form(monkeypatch):
+  """(d) 8 + 9 replayed steps with learning_rate = 0: the state is the closed form of seventeen times the probe's
+  gradient, every loss column the probe's loss."""
+  problem = _problem(GRAPH)
+  eng = _handle(GRAPH, problem, monkeypatch, learning_rate=0.0, env=(('BNF_GRAPH', '1'),))
+  probe = _handle(GRAPH, problem, monkeypatch, learning_rate=0.0)
+  theta0 = _init(eng, problem)
+  probe.set_params(theta0)
+  l1 = eng.train(0, 8)
+  l2 = eng.train(8, 9)
+  torch.cuda.synchronize()
+  losses = np.concatenate([l1.cpu().numpy(), l2.cpu().numpy()], axis=1)
+  loss_p, g = probe.debug_loss_and_grad(0, 0)
+  np.testing.assert_array_equal(eng.get_params(), theta0)
+  _assert_live(GRAPH, problem[1], g)
+  _check_state(problem[1], _state(eng), [R.moments([g] * 17)], _bar(GRAPH), 'graph, frozen')
+  np.testing.assert_allclose(losses, np.repeat(loss_p[:, None], 17, axis=1), rtol=LOSS_RTOL)
+  eng.close(); probe.close()
+
+
+def test_graph_replay_moving_run_equals_eager(monkeypatch):
+  """(d) 8 + 9 steps replayed against the eager loop (which (b) holds step by step at this geometry): losses and
+  parameters at the bars of test_graph_replayed_training_equals_eager (1e-5), the state at the moment bars."""
+  problem = _problem(GRAPH)
+  out = {}
+  for mode in ('0', '1'):
+    eng = _handle(GRAPH, problem, monkeypatch, env=(('BNF_GRAPH', mode),))
+    _init(eng, problem)
+    l1 = eng.train(0, 8)
+    l2 = eng.train(8, 9)
+    torch.cuda.synchronize()
+    out[mode] = (np.concatenate([l1.cpu().numpy(), l2.cpu().numpy()], axis=1), eng.get_params().copy(), _state(eng))
+    eng.close()
+  np.testing.assert_allclose(out['1'][0], out['0'][0], rtol=1e-5)
+  assert util.rel_err(out['1'][1], out['0'][1]) < 1e-5, util.rel_err(out['1'][1], out['0'][1])
+  _check_state(problem[1], out['1'][2], [(out['0'][2][0], out['0'][2][1])], _bar(GRAPH), 'graph vs eager state')
