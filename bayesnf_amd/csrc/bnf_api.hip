@@ -44,6 +44,7 @@
 #include "bnf_dependence.h"
 #include "bnf_ranking.h"
 #include "bnf_stacking.h"
+#include "bnf_plan.h"
 
 using namespace bnf;
 
@@ -90,6 +91,8 @@ static constexpr int64_t kAtPad = 128;
 
 struct bnf_handle {
   bnf_config cfg;
+  Switches sw;     // the BNF_* environment, read once at bnf_create (bnf_plan.h)
+  StepPlan plan;   // weight-gradient kernels, their launch order and the optimiser's kept ranges: decided once, at bnf_create
   NetDev nd;
   FreqTab ft;
   bool bf16 = false;
@@ -122,7 +125,6 @@ struct bnf_handle {
   hipStream_t stream2 = nullptr;            // weight-gradient contractions overlap the dgrad chain
   hipEvent_t ev_dz[BNF_MAX_LAYERS] = {};    // dZ_l is complete (main stream)
   hipEvent_t ev_wg = nullptr;               // all weight gradients are complete (stream2)
-  bool overlap = false;   // BNF_OVERLAP=1: measured neutral (3.79 vs 3.76 ms/step), off by default
   bool bound = false;
   int64_t adam_t = 0;  // optimiser step count
   // caller buffers
@@ -152,18 +154,14 @@ struct bnf_handle {
   size_t owned_bytes = 0;        // device memory the engine allocated itself (bnf_owned_bytes)
   int32_t* perm = nullptr; int64_t perm_epoch = -1;      // the current epoch's (members, N) row ids
   int32_t* leaf_off = nullptr; uint8_t* leaf_id = nullptr; int32_t n_leaves = 0;
-  bool adam_clear_all = false;   // env BNF_ADAM_CLEAR_ALL (A/B of the kept gradient range)
   bool h0l = false;
   bool fold0 = false;   // the panel kernel's F0 forms: layer-0 scale / bias folded into its contraction (needs h0l, F + 2 <= Fp)
-  void* A[BNF_MAX_LAYERS]; void* H[BNF_MAX_LAYERS]; void* Ht[BNF_MAX_LAYERS];
-  void* dZ[BNF_MAX_LAYERS]; void* dZt[BNF_MAX_LAYERS];
+  void* A[BNF_MAX_LAYERS]; void* H[BNF_MAX_LAYERS];
+  void* dZ[BNF_MAX_LAYERS];
   void* Kn[BNF_MAX_LAYERS]; void* Kt[BNF_MAX_LAYERS];
   int64_t pack_batch[BNF_MAX_LAYERS];
   float* dH0 = nullptr; float* out = nullptr; float* ybat = nullptr; float* loss_raw = nullptr;
   float* vacc = nullptr; float* dv = nullptr;   // output-layer dot accumulator, d loss / d v
-  // read at bnf_create: BNF_VI_SAMPLE_PACK=0 -> k_vi_sample + k_pack_layers instead of the fused sampler;
-  // BNF_VI_KEEP_Z=1 -> every sample is written to theta_c and k_vi_adam recovers the noise from it (round-3 data flow)
-  bool vi_sample_pack = true, vi_keep_z = false;
   bool panel = false;         // row-panel forward + backward kernel (bnf_panel.h): bf16, depth 2, W = 256 / 512
   void* Wf[BNF_MAX_LAYERS]; void* Wb[BNF_MAX_LAYERS];   // fragment-major packed weights
   void* park[BNF_MAX_LAYERS];                            // row-panel pipeline, depth > 2: parked pre-activations of the middle layers
@@ -174,22 +172,16 @@ struct bnf_handle {
   bool recompute_a0 = false;  // layer-0 pre-activation recomputed in the backward pass (DGRAD TAG 2)
   bool fuse_last = false;     // last layer + likelihood + its backward in one kernel (EPI_LAST)
   int num_cus = 256;          // multiProcessorCount of the device
-  int tn_ring = 1;            // env BNF_TN_RING=0: gemm_tn's two-stage K loop for the 256 x 256 weight-gradient tile
-  int skinny = 1;             // env BNF_WGRAD_SKINNY=0: layer-0 weight gradient through gemm_tn's 128 x 128 tiles
-  int big_tiles = 1;          // env BNF_BIG_TILES: 0 = 128 x 128 tiles everywhere, 1 = auto, 2 = 256 x 256
-                              // wherever the shape divides (tests of the large-tile kernels at small sizes)
   float* scal = nullptr;      // (Ev, kScalStride) transformed scalar leaves (k_member_scalars)
   StepState* step_state = nullptr;   // device: per-step state of the graph-replayed loop
   hipGraphExec_t graph_exec = nullptr;   // one captured full-batch MAP step (launch-bound sizes)
   int64_t graph_cols = 0;     // loss row stride the captured step was recorded with
   float* graph_losses = nullptr;
-  int graph_mode = 0;         // env BNF_GRAPH=1: replay full-batch MAP steps from a hipGraph
   float* qscratch = nullptr;  // quantile partials: 2*1024*2 + 2 floats
   float* dbg_a = nullptr; float* dbg_b = nullptr;  // small debug staging (gmu/grho)
   uint8_t* is_matrix = nullptr;
   size_t ws_bytes = 0;
   // profiling
-  int ablate = 0;      // env BNF_ABLATE, perf experiments only
   uint32_t prof = 0;   // bit k: bracket launches of kernel id k with HIP events
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> event_pool;
@@ -203,7 +195,7 @@ static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * 
 // the H0L panel forms (feature panel staged in LDS) exist for these shapes
 static bool panel_h0l(const bnf_handle* h) {
   const bool shape = ((h->W == 512 || h->W == 1024) && h->Fp == 64) || (h->W == 256 && (h->Fp == 64 || h->Fp == 128));
-  return h->panel && shape && !getenv("BNF_PANEL_NO_H0L");
+  return h->panel && shape && !h->sw.panel_no_h0l;
 }
 
 // carve or just measure (base == nullptr) the workspace layout
@@ -239,9 +231,7 @@ static size_t carve(bnf_handle* h, char* base) {
   for (int l = 0; l < h->L; ++l) {
     h->A[l] = (h->panel || (h->fuse_last && l == h->L - 1) || (h->recompute_a0 && l == 0)) ? nullptr : take((size_t)Ev * W * (Bp + kAtPad) * es);  // A_l^T (W, Bp + pad)
     h->H[l] = (l < h->L - 1) ? take((size_t)Ev * Bp * W * es) : nullptr;       // H_{l+1} (Bp, W)
-    h->Ht[l] = nullptr;
     h->dZ[l] = fo ? nullptr : take((size_t)Ev * Bp * W * es);
-    h->dZt[l] = nullptr;
     const int64_t npad = (l == 0) ? Fp : W;
     h->pack_batch[l] = npad * W;
     h->Kn[l] = h->panel ? nullptr : take((size_t)Ev * npad * W * es);
@@ -296,11 +286,11 @@ struct LaunchScope {
     };
     t0 = get();
     t1 = get();
-    hipEventRecord(t0, h->stream);
+    hipEventRecord(t0, st);
   }
   ~LaunchScope() {
     if (!on) return;
-    hipEventRecord(t1, h->stream);
+    hipEventRecord(t1, st);
     h->timed.push_back({kid, t0, t1});
   }
 };
@@ -327,8 +317,7 @@ static void drain_timers(bnf_handle* h) {
 static void phase_prof_begin(bnf_handle* h, int kid, unsigned blocks, EpiArgs* ep) {
   ep->prof = nullptr;
 #ifdef BNF_ENABLE_ABLATE
-  const char* want = getenv("BNF_PHASE_PROF");
-  if (!want || strcmp(want, kKernelNames[kid]) != 0) return;
+  if (h->sw.phase_prof != kKernelNames[kid]) return;
   if (!h->prof_buf) (void)hipMalloc(&h->prof_buf, (size_t)(1 << 20) * 16 * sizeof(unsigned long long));
   if (blocks > (1u << 20)) return;
   (void)hipMemsetAsync(h->prof_buf, 0, (size_t)blocks * 128, h->stream);
@@ -337,8 +326,7 @@ static void phase_prof_begin(bnf_handle* h, int kid, unsigned blocks, EpiArgs* e
 }
 static void phase_prof_end(bnf_handle* h, int kid, unsigned blocks, int threads) {
 #ifdef BNF_ENABLE_ABLATE
-  const char* want = getenv("BNF_PHASE_PROF");
-  if (!want || strcmp(want, kKernelNames[kid]) != 0 || !h->prof_buf || blocks > (1u << 20)) return;
+  if (h->sw.phase_prof != kKernelNames[kid] || !h->prof_buf || blocks > (1u << 20)) return;
   std::vector<unsigned long long> host((size_t)blocks * 16);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemcpy(host.data(), h->prof_buf, host.size() * 8, hipMemcpyDeviceToHost);
@@ -386,7 +374,7 @@ static void launch_gemm_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
       allow_lds(h, &gemm_nt<T, EPI, TAG, WGM, WGN, kS>, kLds, &attr_done_s);
       const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
       EpiArgs ep2 = ep;
-      ep2.ablate = h->ablate;
+      ep2.ablate = h->sw.ablate;
       phase_prof_begin(h, kid, blocks, &ep2);
       {
         LaunchScope ls(h, kid);
@@ -400,7 +388,7 @@ static void launch_gemm_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
   allow_lds(h, &gemm_nt<T, EPI, TAG, WGM, WGN>, kLds, &attr_done);
   const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
   EpiArgs ep2 = ep;
-  ep2.ablate = h->ablate;
+  ep2.ablate = h->sw.ablate;
   phase_prof_begin(h, kid, blocks, &ep2);
   LaunchScope ls(h, kid);
   hipLaunchKernelGGL((gemm_nt<T, EPI, TAG, WGM, WGN>), dim3(blocks), dim3(64 * WGM * WGN), kLds, h->stream, g, ep2);
@@ -417,7 +405,7 @@ static void launch_gemm(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep) {
   if constexpr (sizeof(T) == 2 && EPI == EPI_FWD) {
     // (layer 0 has a short K loop and, since A_0 is recomputed, writes only H_1: 316 us with
     // 128 x 128 tiles vs 362 us with 256 x 256 at C2)
-    if (g.N % 256 == 0 && g.M >= 256 && h->big_tiles && (g.K >= 256 || h->big_tiles == 2)) {
+    if (g.N % 256 == 0 && g.M >= 256 && h->sw.big_tiles && (g.K >= 256 || h->sw.big_tiles == 2)) {
       launch_gemm_wg<T, EPI, TAG, 4, 4>(h, kid, g, ep);
       return;
     }
@@ -472,7 +460,6 @@ static void launch_gemm_tn_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs&
   LaunchScope ls(h, kid, st, true);
   hipLaunchKernelGGL((gemm_tn<T, TAG, WG>), dim3(blocks), dim3(64 * WG * WG), kLds, st, g, ep);
 }
-enum { WG_TN128 = 0, WG_TN256 = 1, WG_RING = 2, WG_SKINNY = 3 };   // weight-gradient kernels (wgrad_plan)
 // layer-0 weight gradient as a 64 x 512 row stream (gemm_tn_skinny): Fp = 64, W a multiple of 512
 static void launch_gemm_tn_skinny(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep, hipStream_t st) {
   g.tiles_m = 1;
@@ -500,7 +487,7 @@ static void launch_gemm_tn(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
       static std::atomic<uint64_t> attr_done{0}, attr_done_s{0};
       const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk * (g.n_multi > 1 ? g.n_multi : 1));
       EpiArgs ep2 = ep;
-      ep2.ablate = h->ablate;
+      ep2.ablate = h->sw.ablate;
       LaunchScope ls(h, kid, st, true);
       if (g.splitk == 1) {   // plain stores: accumulators transposed, 16-byte stores
         allow_lds(h, &gemm_tn_ring<TAG, true>, kRgLds, &attr_done_s);
@@ -525,7 +512,7 @@ template <int TAG>
 static void launch_gemm_tn8(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep, hipStream_t st, int kind) {
   if (g.splitk < 1) g.splitk = 1;
   EpiArgs ep2 = ep;
-  ep2.ablate = h->ablate;
+  ep2.ablate = h->sw.ablate;
   LaunchScope ls(h, kid, st, true);
   if (kind == WG_SKINNY && TAG == 0) {
     g.tiles_m = 1; g.tiles_n = g.N / 512;
@@ -575,6 +562,27 @@ static void run_pack(bnf_handle* h, const float* theta, int nmem) {
                      (int64_t)h->Pf, jb, (int32_t)h->W, (int32_t)(sizeof(T) == 4 && h->f32_split ? 1 : 0), h->nd, h->scal);
 }
 
+// Hidden layer l's forward contraction H_l . K_l^T / sqrt(fan_in_l) and the parameter side of its epilogue; the caller
+// adds where the results go (run_forward: activations; run_backward's one-kernel last layer: the likelihood's outputs)
+static void fwd_layer_args(const bnf_handle* h, const float* theta, int nmem, int64_t rows, int l, GemmArgs* g, EpiArgs* ep) {
+  const int64_t Bp = h->Bp;
+  g->A = (l == 0) ? h->H0 : h->H[l - 1];
+  g->a_ld = (l == 0) ? h->Fp : h->W;
+  g->a_batch = Bp * g->a_ld;
+  g->B = h->Kt[l];
+  g->b_ld = g->a_ld;
+  g->b_batch = h->pack_batch[l];
+  g->M = (int)rows; g->N = h->W; g->K = g->a_ld; g->splitk = 1; g->members = nmem;
+  ep->theta = theta; ep->theta_stride = h->Pf;
+  ep->scale = 1.0f / sqrtf((float)((l == 0) ? h->F : h->Wt));
+  ep->off_bias = h->nd.off_bias[l];
+  ep->off_layer_scale = h->nd.off_ls[l];
+  ep->off_act_weight = h->nd.off_law;
+  ep->scal = h->scal; ep->scal_stride = kScalStride; ep->layer = l;
+  ep->off_ko = h->nd.off_kernel[h->L];
+  ep->act_batch = Bp * h->W; ep->ld = h->W;
+}
+
 // featurise + forward contractions for `rows` batch rows of `nmem` (virtual)
 // members; leaves vacc[row] = H_L[row] . k_o for the row-loss kernel.
 template <typename T>
@@ -597,33 +605,13 @@ static void run_forward(bnf_handle* h, const float* theta, int nmem, const RowSr
   for (int l = 0; l < n_layers; ++l) {
     const bool last = l == h->L - 1;
     GemmArgs g{};
-    g.A = (l == 0) ? h->H0 : h->H[l - 1];
-    g.a_ld = (l == 0) ? h->Fp : h->W;
-    g.a_batch = Bp * g.a_ld;
-    g.B = h->Kt[l];
-    g.b_ld = (l == 0) ? h->Fp : h->W;
-    g.b_batch = h->pack_batch[l];
-    g.M = (int)rows;
-    g.N = h->W;
-    g.K = (l == 0) ? h->Fp : h->W;
-    g.splitk = 1;
-    g.members = nmem;
     EpiArgs ep{};
-    ep.theta = theta;
-    ep.theta_stride = h->Pf;
-    ep.scale = 1.0f / sqrtf((float)((l == 0) ? h->F : h->Wt));
-    ep.off_bias = h->nd.off_bias[l];
-    ep.off_layer_scale = h->nd.off_ls[l];
-    ep.off_act_weight = h->nd.off_law;
-    ep.scal = h->scal; ep.scal_stride = kScalStride; ep.layer = l;
+    fwd_layer_args(h, theta, nmem, rows, l, &g, &ep);
     ep.out_a = h->A[l];   // null: not materialised in this pipeline
     ep.out_h = last ? nullptr : h->H[l];
     ep.vdot = last ? h->vacc : nullptr;
     ep.vdot_batch = Bp;
-    ep.off_ko = h->nd.off_kernel[h->L];
-    ep.act_batch = Bp * h->W;
     ep.actt_batch = (int64_t)h->W * (Bp + kAtPad);
-    ep.ld = h->W;
     ep.ldt = (int32_t)(Bp + kAtPad);
     if (l == 0) launch_gemm<T, EPI_FWD, 0>(h, KID_FWD0, g, ep);
     else launch_gemm<T, EPI_FWD, 1>(h, KID_FWD, g, ep);
@@ -636,59 +624,15 @@ struct LossSink {
   const StepState* st = nullptr;               // graph replay: per-step state in device memory
 };
 
-// Which kernel computes layer l's weight gradient and with what split-K (1: the kernel STORES dK_l, > 1: f32
-// atomics).  ONE function decides for the launcher (run_wgrad_layer) and for the optimiser, which leaves the range
-// of a stored gradient uncleared (step_map): the two cannot disagree.
-struct WgradPlan { int kind, splitk; };
-static WgradPlan wgrad_plan(const bnf_handle* h, int nmem, int l) {
-  const int M = (l == 0) ? h->F : h->W, N = h->W, a_ld = (l == 0) ? h->Fp : h->W;
-  const int64_t K = h->Bp;
-  const int tiles = ((M + kBM - 1) / kBM) * ((N + kBN - 1) / kBN);
-  const int nk = (int)(K / (h->bf16 ? 64 : 32));
-  const int sk = (1024 + nmem * tiles - 1) / (nmem * tiles);
-  const int base_sk = std::max(1, std::min(sk, std::max(1, nk / 4)));
-  if (h->bf16 && l == 0 && h->skinny && a_ld == 64 && N % 512 == 0 && K % 64 == 0) {
-    // layer 0 as a 64 x 512 row stream, one workgroup per CU (144 KiB of LDS): the K split with the shortest
-    // schedule -- rounds of the chip x rows per workgroup (C3/8, 80 members: 3 splits = 240 workgroups in one round
-    // instead of 4 = 320 in two, the second a quarter full); ties go to the fewest splits (fewest atomics)
-    const int64_t base = (int64_t)nmem * (N / 512);
-    const int nks = (int)(K / kSkRows);
-    const int max_s = (int)std::max<int64_t>(1, std::min<int64_t>((h->num_cus + base - 1) / base, std::max(1, nks / 8)));
-    int best = 1;
-    double best_cost = 1e30;
-    for (int sp = 1; sp <= max_s; ++sp) {
-      const int64_t rounds = (base * sp + h->num_cus - 1) / h->num_cus;
-      const double cost = (double)rounds * (double)((nks + sp - 1) / sp);
-      if (cost < best_cost * 0.98) { best_cost = cost; best = sp; }
-    }
-    return {WG_SKINNY, best};
-  }
-  // 256 x 256 tiles when they still fill the chip (members x tiles >= half the CUs)
-  if (h->big_tiles && M % 256 == 0 && N % 256 == 0) {
-    const int64_t units = (int64_t)nmem * (M / 256) * (N / 256);
-    if (units < 128 && h->big_tiles != 2 && h->bf16 && h->tn_ring && K % 64 == 0 && K >= 16384) {
-      // few large units with a long batch (C5/8: 64 members x one 256 x 256 tile x 71k rows): the ring kernel with K split
-      // until the chip is full -- every operand byte is read ONCE (four 128 x 128 tiles read each half twice), and
-      // the atomics of the splits (256 x 256 floats each) are nothing next to 2 x K x 256 operand elements
-      const int sp = (int)std::min<int64_t>((h->num_cus + units - 1) / units, K / 4096);
-      if (sp >= 1) return {WG_RING, std::max(1, sp)};
-    }
-    if (units >= 128 || h->big_tiles == 2) {
-      if (h->bf16 && h->tn_ring && K % 64 == 0) {
-        // the four-stage ring, one workgroup per CU, NO split-K: splitting to shorten the last, partly filled
-        // round of workgroups was measured at C3/8 (320 tiles on 256 CUs) -- 2 splits 230 -> 300 us per launch,
-        // 4 splits 438 us, 5,680 -> 5,290 -> 4,730 member-steps/s: the f32 atomics of 80 x 512 x 512 outputs
-        // per split cost far more than the idle quarter round (gpurun_out/r03n).  BNF_RING_SPLITK forces one.
-        int best = 1;
-        if (const char* fs = getenv("BNF_RING_SPLITK")) best = std::max(1, atoi(fs));
-        return {WG_RING, best};
-      }
-      return {WG_TN256, base_sk};
-    }
-  }
-  return {WG_TN128, base_sk};
+static_assert(kPlanBM == kBM && kPlanBN == kBN && kPlanSkRows == kSkRows, "bnf_plan.h counts tiles of the kernels' sizes");
+
+static PlanShape plan_shape(const bnf_handle* h) {
+  PlanShape ps{};
+  ps.bf16 = h->bf16; ps.L = h->L; ps.W = h->W; ps.F = h->F; ps.Fp = h->Fp; ps.Bp = h->Bp;
+  ps.num_cus = h->num_cus; ps.panel = h->panel; ps.pad = h->pad;
+  for (int l = 0; l < h->L; ++l) ps.off_kernel[l] = h->nd.off_kernel[l];
+  return ps;
 }
-static int wgrad_splitk(const bnf_handle* h, int nmem, int l) { return wgrad_plan(h, nmem, l).splitk; }
 
 // weight gradient of layer l from the row-major H_l / dZ_l left in HBM, on stream `st`
 template <typename T>
@@ -701,7 +645,7 @@ static void run_wgrad_layer(bnf_handle* h, int nmem, int l, hipStream_t st) {
   g.a_ld = (l == 0) ? h->Fp : h->W; g.a_batch = Bp * g.a_ld;
   g.B = h->dZ[l]; g.b_ld = h->W; g.b_batch = Bp * h->W;
   g.M = (l == 0) ? h->F : h->W; g.N = h->W; g.K = (int)Bp; g.members = nmem;
-  const WgradPlan plan = wgrad_plan(h, nmem, l);
+  const WgradPlan plan = h->plan.layer[l];
   g.splitk = plan.splitk;
   EpiArgs ep{};
   ep.scale = 1.0f / sqrtf((float)((l == 0) ? h->F : h->Wt));
@@ -726,7 +670,7 @@ static void run_wgrad_layer(bnf_handle* h, int nmem, int l, hipStream_t st) {
 // stream (or in line when overlap is off / unavailable)
 template <typename T>
 static void wgrad_after_dz(bnf_handle* h, int nmem, int l) {
-  if (h->overlap && h->stream2) {
+  if (h->sw.overlap && h->stream2) {
     (void)hipEventRecord(h->ev_dz[l], h->stream);
     (void)hipStreamWaitEvent(h->stream2, h->ev_dz[l], 0);
     run_wgrad_layer<T>(h, nmem, l, h->stream2);
@@ -736,62 +680,39 @@ static void wgrad_after_dz(bnf_handle* h, int nmem, int l) {
 }
 // before the optimiser: every weight gradient must have landed
 static void wgrad_join(bnf_handle* h) {
-  if (h->overlap && h->stream2) {
+  if (h->sw.overlap && h->stream2) {
     (void)hipEventRecord(h->ev_wg, h->stream2);
     (void)hipStreamWaitEvent(h->stream, h->ev_wg, 0);
   }
 }
 
 // the W x W weight gradients of layers 1 .. L-1 as ONE launch of the ring kernel (same shape, same split-K = 1):
-// 3 x 320 tiles at C3/8 are 4 rounds of the chip instead of 3 x 2
-static bool wgrad_multi_ok(const bnf_handle* h, int nmem) {
-  if (!h->bf16 || h->L < 3 || h->overlap || getenv("BNF_WGRAD_NO_MULTI")) return false;
+// 3 x 320 tiles at C3/8 are 4 rounds of the chip instead of 3 x 2 (StepPlan::merged)
+static void run_wgrad_merged(bnf_handle* h, int nmem) {
+  const int64_t Bp = h->Bp;
+  GemmArgs g{};
+  g.a_ld = h->W; g.a_batch = Bp * h->W; g.b_ld = h->W; g.b_batch = Bp * h->W;
+  g.M = h->W; g.N = h->W; g.K = (int)Bp; g.members = nmem; g.splitk = 1;
+  g.n_multi = h->L - 1;
   for (int l = 1; l < h->L; ++l) {
-    const WgradPlan p = wgrad_plan(h, nmem, l);
-    if (p.kind != WG_RING || p.splitk != 1) return false;
+    g.A_multi[l - 1] = h->H[l - 1]; g.B_multi[l - 1] = h->dZ[l]; g.off_out_multi[l - 1] = h->nd.off_kernel[l];
   }
-  // only where it saves rounds of the chip (C3/8: 3 x 320 tiles = 4 rounds instead of 6, +6.6 % on the step; C4/8:
-  // 3 x 512 tiles = 6 rounds either way and the merged launch measured 1 % slower -- gpurun_out/r03q)
-  const int64_t units = (int64_t)nmem * (h->W / 256) * (h->W / 256), cus = h->num_cus, n = h->L - 1;
-  return (n * units + cus - 1) / cus < n * ((units + cus - 1) / cus);
-}
-template <typename T>
-static void run_wgrad(bnf_handle* h, int nmem) {
-  if constexpr (sizeof(T) == 2) {
-    if (wgrad_multi_ok(h, nmem)) {
-      const bool l0_first = getenv("BNF_WGRAD_ORDER") && !strcmp(getenv("BNF_WGRAD_ORDER"), "fwd");   // (see below)
-      if (l0_first) wgrad_after_dz<T>(h, nmem, 0);
-      const int64_t Bp = h->Bp;
-      GemmArgs g{};
-      g.a_ld = h->W; g.a_batch = Bp * h->W; g.b_ld = h->W; g.b_batch = Bp * h->W;
-      g.M = h->W; g.N = h->W; g.K = (int)Bp; g.members = nmem; g.splitk = 1;
-      g.n_multi = h->L - 1;
-      for (int l = 1; l < h->L; ++l) {
-        g.A_multi[l - 1] = h->H[l - 1]; g.B_multi[l - 1] = h->dZ[l]; g.off_out_multi[l - 1] = h->nd.off_kernel[l];
-      }
-      g.A = g.A_multi[0]; g.B = g.B_multi[0];
-      EpiArgs ep{};
-      ep.scale = 1.0f / sqrtf((float)h->Wt);
-      ep.grad = h->gradf; ep.grad_stride = h->Pf; ep.off_out = h->nd.off_kernel[1]; ep.ld_f32 = h->W;
-      if (h->q8) {
-        ep.qscale = h->qscale;
-        launch_gemm_tn8<1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
-      } else {
-        launch_gemm_tn<T, 1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
-      }
-      if (!l0_first) wgrad_after_dz<T>(h, nmem, 0);
-      return;
-    }
-  }
-  // Order: the LAST layer's weight gradient first.  In the panel pipeline every dZ_l exists when this runs, and the
-  // panel kernel wrote dZ_0 last: read right away it comes back at two thirds of the HBM rate (dirty lines in the
-  // memory-side cache, profiles/r02w_wgrad_streams.md); after the W x W kernels have streamed their operands it does not.
-  // (BNF_WGRAD_ORDER=fwd: layer 0 first, the order of rounds 1 - 3.)
-  static const bool fwd_order = getenv("BNF_WGRAD_ORDER") && !strcmp(getenv("BNF_WGRAD_ORDER"), "fwd");
-  if (fwd_order || !h->panel) {
-    for (int l = 0; l < h->L; ++l) wgrad_after_dz<T>(h, nmem, l);
+  g.A = g.A_multi[0]; g.B = g.B_multi[0];
+  EpiArgs ep{};
+  ep.scale = 1.0f / sqrtf((float)h->Wt);
+  ep.grad = h->gradf; ep.grad_stride = h->Pf; ep.off_out = h->nd.off_kernel[1]; ep.ld_f32 = h->W;
+  if (h->q8) {
+    ep.qscale = h->qscale;
+    launch_gemm_tn8<1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
   } else {
-    for (int l = h->L - 1; l >= 0; --l) wgrad_after_dz<T>(h, nmem, l);
+    launch_gemm_tn<bf16_t, 1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
+  }
+}
+// the row-panel pipeline's weight gradients, in the plan's order (every dZ_l exists when this runs)
+static void run_wgrad(bnf_handle* h, int nmem) {
+  for (int i = 0; i < h->plan.n_launch; ++i) {
+    if (h->plan.launch[i] == kWgradMerged) run_wgrad_merged(h, nmem);
+    else wgrad_after_dz<bf16_t>(h, nmem, h->plan.launch[i]);
   }
   wgrad_join(h);
 }
@@ -808,23 +729,10 @@ static void run_backward(bnf_handle* h, const float* theta, int nmem, const RowS
     // row-loss and last-backward kernels produce
     const int l = L - 1;
     GemmArgs g{};
-    g.A = (l == 0) ? h->H0 : h->H[l - 1];
-    g.a_ld = (l == 0) ? h->Fp : h->W;
-    g.a_batch = Bp * g.a_ld;
-    g.B = h->Kt[l];
-    g.b_ld = g.a_ld;
-    g.b_batch = h->pack_batch[l];
-    g.M = (int)rows; g.N = h->W; g.K = g.a_ld; g.splitk = 1; g.members = nmem;
     EpiArgs ep{};
-    ep.theta = theta; ep.theta_stride = h->Pf;
-    ep.scale = 1.0f / sqrtf((float)((l == 0) ? h->F : h->Wt));
-    ep.off_bias = h->nd.off_bias[l];
-    ep.off_layer_scale = h->nd.off_ls[l];
-    ep.off_act_weight = h->nd.off_law;
-    ep.scal = h->scal; ep.scal_stride = kScalStride; ep.layer = l;
-    ep.off_ko = h->nd.off_kernel[L]; ep.inv_sw = 1.0f / sqrtf((float)h->Wt);
+    fwd_layer_args(h, theta, nmem, rows, l, &g, &ep);
+    ep.inv_sw = 1.0f / sqrtf((float)h->Wt);
     ep.out_h = h->dZ[l];
-    ep.act_batch = Bp * h->W; ep.ld = h->W;
     ep.grad = h->gradf; ep.grad_stride = h->Pf;
     ep.ybat = h->ybat; ep.row_batch = Bp;
     ep.out = h->out; ep.out_batch = Bp;
@@ -954,7 +862,7 @@ static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
   static std::atomic<uint64_t> attr_done{0};
   allow_lds(h, &k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8>, kLds, &attr_done);
   PanelArgs pa2 = pa;
-  pa2.ablate = h->ablate;
+  pa2.ablate = h->sw.ablate;
   const unsigned blocks = (unsigned)(pa.members * pa.panels);
   {
     EpiArgs tmp{};
@@ -1072,7 +980,7 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
                        (int64_t)h->Pf, h->scal, h->B, h->dH0, (int64_t)h->Fp * Bp, (int32_t)Bp, h->gradf,
                        (int64_t)h->Pf);
   }
-  run_wgrad<bf16_t>(h, nmem);
+  run_wgrad(h, nmem);
 }
 
 // parameters as the forward / backward kernels read them (padded copy when the width is padded)
@@ -1212,6 +1120,12 @@ static int ensure_row_perm(bnf_handle* h, int64_t epoch) {
   return BNF_OK;
 }
 
+// Adam's bias corrections at step t (the graph-replayed loop advances them on the device: k_step_advance)
+static void adam_bias(int64_t t, float* bc1, float* bc2) {
+  *bc1 = (float)(1.0 - std::pow(0.9, (double)t));
+  *bc2 = (float)(1.0 - std::pow(0.999, (double)t));
+}
+
 // One MAP/MLE step.  apply=false: leave params untouched, grad holds the full
 // gradient (likelihood + prior), loss_raw the step loss.
 template <typename T>
@@ -1234,19 +1148,13 @@ static int step_map(bnf_handle* h, int64_t epoch, int64_t step, const LossSink& 
   a.stride = h->P; a.P = h->P; a.off_shape = h->nd.off_shape;
   const int64_t t = h->adam_t + 1;
   a.lr = h->cfg.learning_rate;
-  a.bc1 = (float)(1.0 - std::pow(0.9, (double)t));
-  a.bc2 = (float)(1.0 - std::pow(0.999, (double)t));
+  adam_bias(t, &a.bc1, &a.bc2);
   a.prior_weight = h->cfg.prior_weight;
   a.loss = sink.loss; a.loss_stride = sink.stride; a.loss_scale = sink.scale;
   a.apply = apply ? 1 : 0; a.loss_raw = sink.raw; a.st = sink.st;
-  // the largest hidden-layer kernel whose gradient the next step stores (no split-K) is not cleared
-  a.keep_lo = a.keep_hi = 0;
-  if (!h->pad && !h->adam_clear_all && h->ablate == 0)
-    for (int l = 1; l < h->L; ++l)
-      if (wgrad_splitk(h, E, l) == 1 && a.keep_hi == 0) {
-        a.keep_lo = (h->nd.off_kernel[l] + 3) / 4 * 4;
-        a.keep_hi = (h->nd.off_kernel[l] + h->W * h->W) / 4 * 4;
-      }
+  // the hidden-layer kernel whose gradient the next step stores (no split-K) is not cleared
+  a.keep_lo = h->plan.n_keep ? h->plan.keep_lo[0] : 0;
+  a.keep_hi = h->plan.n_keep ? h->plan.keep_hi[0] : 0;
   {
     LaunchScope ls(h, KID_ADAM);
     hipLaunchKernelGGL(k_adam_map, dim3(cdiv(cdiv(h->P, 4), 256 * BNF_ADAM_QUADS), (unsigned)E), dim3(256), 0, h->stream, a);
@@ -1280,7 +1188,7 @@ static dim3 vi_sample_grid(const ViSegs& sg, int members) {
 // k_vi_sample_pack: row-panel pipeline on the parameter layout itself (no padded copy), every hidden kernel starting on
 // a quad boundary of the noise stream (always, with spec.py's layout), BNF_VI_SAMPLE_PACK=0 restores the two kernels
 static bool vi_sample_pack_ok(const bnf_handle* h) {
-  if (!h->vi_sample_pack || !h->panel || h->pad || h->W % 64 != 0) return false;
+  if (!h->sw.vi_sample_pack || !h->panel || h->pad || h->W % 64 != 0) return false;
   for (int l = 0; l < h->L; ++l)
     if ((h->nd.off_kernel[l] + kEpsQuadPhase) % 4 != 0) return false;
   return true;
@@ -1322,7 +1230,7 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
       const PackJobs jb = pack_jobs(h, &tiles);
       ViSampleArgs sa{};
       sa.mu = mu; sa.rho = rho; sa.P = h->P; sa.S = S; sa.seed = h->cfg.seed; sa.member_offset = h->cfg.member_offset;
-      sa.step = (uint64_t)step; sa.z = h->theta_c; sa.write_z = h->vi_keep_z ? 1 : 0;
+      sa.step = (uint64_t)step; sa.z = h->theta_c; sa.write_z = h->sw.vi_keep_z ? 1 : 0;
       hipLaunchKernelGGL((k_vi_sample_pack<bf16_t, BNF_VI_SP_THREADS>), dim3((unsigned)tiles * (unsigned)E),
                          dim3(BNF_VI_SP_THREADS), 0, h->stream, sa, jb,
                          h->nd, h->scal);
@@ -1348,22 +1256,15 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
   a.seed = h->cfg.seed; a.member_offset = h->cfg.member_offset; a.step = (uint64_t)step;
   const int64_t t = h->adam_t + 1;
   a.lr = h->cfg.learning_rate;
-  a.bc1 = (float)(1.0 - std::pow(0.9, (double)t));
-  a.bc2 = (float)(1.0 - std::pow(0.999, (double)t));
+  adam_bias(t, &a.bc1, &a.bc2);
   a.kl_weight = kl; a.loss = loss; a.loss_stride = loss_stride; a.apply = apply ? 1 : 0;
   a.gmu_out = gmu_out; a.grho_out = grho_out; a.ext_eps = h->ext_eps; a.jn = jn;
   // the device generator's noise is made again in k_vi_adam (one Philox call per sample and quad); the caller's or the
   // reference's stream is recovered from the samples in theta_c
-  a.z = (!h->ext_eps && !jn.keys && !h->vi_keep_z) ? nullptr : h->theta_c;
+  a.z = (!h->ext_eps && !jn.keys && !h->sw.vi_keep_z) ? nullptr : h->theta_c;
   // the Dense kernels whose gradient the next step's weight-gradient kernel stores (split-K = 1) need no clearing
-  a.n_keep = 0;
-  if (!h->pad && !h->adam_clear_all && h->ablate == 0)
-    for (int l = 0; l < h->L; ++l)
-      if (wgrad_splitk(h, h->Ev, l) == 1) {
-        a.keep_lo[a.n_keep] = h->nd.off_kernel[l];
-        a.keep_hi[a.n_keep] = h->nd.off_kernel[l] + ((l == 0) ? h->F : h->W) * h->W;
-        ++a.n_keep;
-      }
+  a.n_keep = h->plan.n_keep;
+  for (int r = 0; r < a.n_keep; ++r) { a.keep_lo[r] = h->plan.keep_lo[r]; a.keep_hi[r] = h->plan.keep_hi[r]; }
   {
     LaunchScope ls(h, KID_VIADAM);
     dim3 grid(cdiv(cdiv(h->P + kEpsQuadPhase, 4), 256), (unsigned)E);
@@ -1594,18 +1495,11 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
     h->ft.h[j] = cfg->harmonic[j];
   }
   for (int k = 0; k < KID_COUNT; ++k) { h->acc_ms[k] = 0; h->acc_calls[k] = 0; }
-  if (const char* ab = getenv("BNF_ABLATE")) h->ablate = atoi(ab);
+  h->sw = read_switches(getenv);   // the one read of the environment: every switch belongs to the handle from here on
   h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (const char* bt = getenv("BNF_BIG_TILES")) h->big_tiles = atoi(bt);
-  if (const char* sk = getenv("BNF_WGRAD_SKINNY")) h->skinny = atoi(sk);
-  if (const char* rg = getenv("BNF_TN_RING")) h->tn_ring = atoi(rg);
-  if (const char* gm = getenv("BNF_GRAPH")) h->graph_mode = atoi(gm);
-  h->adam_clear_all = getenv("BNF_ADAM_CLEAR_ALL") != nullptr;
-  if (const char* v = getenv("BNF_VI_SAMPLE_PACK")) h->vi_sample_pack = atoi(v) != 0;
-  if (const char* v = getenv("BNF_VI_KEEP_Z")) h->vi_keep_z = atoi(v) != 0;
   {
-    int want = cfg->pipeline;  // 0 auto, 1 layer kernels with every activation materialised, 3 row-panel kernel
-    if (const char* pf = getenv("BNF_PIPELINE")) want = atoi(pf);
+    // 0 auto, 1 layer kernels with every activation materialised, 3 row-panel kernel
+    const int want = h->sw.pipeline_set ? h->sw.pipeline : cfg->pipeline;
     if (want != 0 && want != 1 && want != 3) {
       delete h;
       return fail(BNF_ERR_INVALID, "pipeline %d (0 auto, 1 layers, 3 panel)", want);
@@ -1627,7 +1521,7 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
     if (h->panel) h->Bp = align_up(h->B, 256);
     // fp8 W x W contractions (PanelArgs.c8): every folded row-panel form (W = 256 / 512 / 1024, any depth >= 2);
     // BNF_FP8_CONTRACT=0 keeps the round-5 arithmetic (bf16 contractions, fp8 copies only)
-    h->c8 = h->q8 && h->panel && !(getenv("BNF_FP8_CONTRACT") && atoi(getenv("BNF_FP8_CONTRACT")) == 0);
+    h->c8 = h->q8 && h->panel && h->sw.fp8_contract;
     // pipeline 0 (auto): layer kernels with the one-kernel last layer where the width allows;
     // pipeline 1: every layer kernel separate and every activation materialised (validation)
     const bool fl_ok = h->bf16 ? fused_last_supported<bf16_t>(h->W) : fused_last_supported<float>(h->W);
@@ -1636,10 +1530,9 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
     h->recompute_a0 = !cfg->forward_only && !h->panel && want == 0 && h->L >= 2 && h->Fp <= 128;
   }
   h->h0l = panel_h0l(h);
-  h->fold0 = h->h0l && h->F + 2 <= h->Fp && !(getenv("BNF_PANEL_FOLD0") && atoi(getenv("BNF_PANEL_FOLD0")) == 0);
+  h->fold0 = h->h0l && h->F + 2 <= h->Fp && h->sw.panel_fold0;
   h->c8 = h->c8 && h->fold0;     // (the fp8-contraction kernels are instantiated for the folded forms: every BASELINE layout)
-  if (h->h0l &&
-      !(getenv("BNF_PANEL_FEATBWD") && atoi(getenv("BNF_PANEL_FEATBWD")) == 0)) {
+  if (h->h0l && h->sw.panel_featbwd) {
     // fused featurisation backward of the H0L panel kernel: what each feature column contributes
     int in_group = -1;
     for (int g = 0; g < cfg->n_groups; ++g)
@@ -1682,6 +1575,7 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
       h->fb_in_group = in_group;
     }
   }
+  h->plan = make_step_plan(plan_shape(h), h->sw, h->Ev, cfg->mode == BNF_MODE_VI);   // (num_cus, panel and Bp are final)
   h->ws_bytes = carve(h, nullptr);
   *out = h;
   return BNF_OK;
@@ -1702,7 +1596,7 @@ void bnf_destroy(bnf_handle* h) {
   if (h->prof_buf) {
     if (h->prof_blocks > 0) {
       fprintf(stderr, "[phase clocks] %s: %d threads/workgroup, mean cycles per workgroup: total %.0f |",
-              getenv("BNF_PHASE_PROF"), h->prof_threads, h->prof_gap[0] / h->prof_blocks);
+              h->sw.phase_prof.c_str(), h->prof_threads, h->prof_gap[0] / h->prof_blocks);
       for (int k = 1; k < 16; ++k) fprintf(stderr, " m%d %.0f", k, h->prof_gap[k] / h->prof_blocks);
       fprintf(stderr, "\n");
     }
@@ -1765,7 +1659,6 @@ int bnf_bind(bnf_handle* h, void* params, void* opt_state, void* workspace, cons
   }
   HIPCHK(hipGetLastError());
   if (!h->stream2 && !h->cfg.forward_only) {
-    if (const char* ov = getenv("BNF_OVERLAP")) h->overlap = atoi(ov) != 0;
     HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     for (int l = 0; l < h->L; ++l) HIPCHK(hipEventCreateWithFlags(&h->ev_dz[l], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_wg, hipEventDisableTiming));
@@ -1847,13 +1740,12 @@ int bnf_train(bnf_handle* h, int64_t epoch0, int64_t num_epochs, float* losses) 
     // replay 135 us vs 131 us eager -- the C loop already runs ahead of the GPU (11 launches x
     // ~3.5 us of host time), the step is bound by its ~11 DEPENDENT kernel boundaries on the device,
     // which a graph does not remove.  Hence opt-in; the lever for this regime is fewer kernels.
-    const bool graph_ok = h->B >= h->N && !h->prof && !h->overlap && h->stream2 && num_epochs >= 8 &&
-                          h->graph_mode == 1;   // opt-in (BNF_GRAPH=1): measured neutral, see below
+    const bool graph_ok = h->B >= h->N && !h->prof && !h->sw.overlap && h->stream2 && num_epochs >= 8 &&
+                          h->sw.graph_mode == 1;   // opt-in (BNF_GRAPH=1): measured neutral, see below
     if (graph_ok) {
       StepState st0{};
       st0.t = h->adam_t + 1; st0.col = 0;
-      st0.bc1 = (float)(1.0 - std::pow(0.9, (double)st0.t));
-      st0.bc2 = (float)(1.0 - std::pow(0.999, (double)st0.t));
+      adam_bias(st0.t, &st0.bc1, &st0.bc2);
       HIPCHK(hipMemcpyAsync(h->step_state, &st0, sizeof(st0), hipMemcpyHostToDevice, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));   // st0 lives on this stack frame
       if (!h->graph_exec || h->graph_cols != num_epochs || h->graph_losses != losses) {
@@ -2778,9 +2670,9 @@ int bnf_debug_gemm_nt(bnf_handle* h, const float* A, const float* Bt, int32_t M,
 
 // the raw weight-gradient core on a caller's shape: the tile the production dispatch would pick for it
 static int debug_tn_kind(const bnf_handle* h, const GemmArgs& g) {
-  if (h->big_tiles && g.M % 256 == 0 && g.N % 256 == 0 &&
-      ((int64_t)g.members * (g.M / 256) * (g.N / 256) >= 128 || h->big_tiles == 2))
-    return (h->bf16 && h->tn_ring && g.K % 64 == 0) ? WG_RING : WG_TN256;
+  if (h->sw.big_tiles && g.M % 256 == 0 && g.N % 256 == 0 &&
+      ((int64_t)g.members * (g.M / 256) * (g.N / 256) >= 128 || h->sw.big_tiles == 2))
+    return (h->bf16 && h->sw.tn_ring && g.K % 64 == 0) ? WG_RING : WG_TN256;
   return WG_TN128;
 }
 
@@ -2802,7 +2694,8 @@ int bnf_debug_gemm_tn(bnf_handle* h, const float* A, const float* B, int32_t R, 
     // A -> e4m3, B -> e5m2 (saturating, round to nearest even), then the fp8 kernel of the kind BNF_DEBUG_TN_KIND names
     // (0: the generic 128 x 128 tile, 2: ring -- M, N multiples of 256 --, 3: skinny -- M = 64, N a multiple of 512),
     // split-K BNF_DEBUG_TN_SPLITK: tests/test_gpu_fp8.py checks every kernel against the host product of the same
-    // quantised operands
+    // quantised operands.  (The two variables are arguments of THIS debug call, read when it is made -- not handle
+    // state, so not in Switches.)
     const int kind = getenv("BNF_DEBUG_TN_KIND") ? atoi(getenv("BNF_DEBUG_TN_KIND")) : WG_TN128;
     g.splitk = getenv("BNF_DEBUG_TN_SPLITK") ? std::max(1, atoi(getenv("BNF_DEBUG_TN_SPLITK"))) : 1;
     if ((kind == WG_RING && (M % 256 || N % 256)) || (kind == WG_SKINNY && (M != 64 || N % 512)) ||
@@ -3067,7 +2960,7 @@ double bnf_kernel_flops(const bnf_handle* h, const char* name) {
   const double Ev = h->Ev, B = (double)h->B, W = h->Wt, F = h->F;
   if (!strcmp(name, "gemm_fwd_l0") || !strcmp(name, "gemm_dgrad0") || !strcmp(name, "gemm_wgrad_l0"))
     return 2.0 * Ev * B * F * W;
-  if (!strcmp(name, "gemm_wgrad") && h->panel && wgrad_multi_ok(h, h->Ev))   // one launch for the layers 1 .. L-1
+  if (!strcmp(name, "gemm_wgrad") && h->plan.merged)   // one launch for the layers 1 .. L-1
     return 2.0 * Ev * B * W * W * (h->L - 1);
   if (!strcmp(name, "gemm_fwd") || !strcmp(name, "gemm_dgrad") || !strcmp(name, "gemm_wgrad"))
     return 2.0 * Ev * B * W * W;

@@ -1,0 +1,193 @@
+// bnf_plan.h -- what a handle decides ONCE, at bnf_create: the environment switches (Switches) and the weight-gradient
+// side of the training step (StepPlan).  Host only, plain C++17, no HIP headers: tests/test_step_plan_host.py compiles
+// this file with g++ and asserts the plans without a GPU.
+//
+// The step functions of bnf_api.hip execute h->plan; nothing on the step path reads the environment or derives a
+// kernel choice again.  The launcher and the optimiser therefore cannot disagree about which gradient ranges the next
+// step's kernels STORE (split-K 1) and which they accumulate into, whatever happens to the environment in between.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../include/bnf.h"
+
+namespace bnf {
+
+// ---- switches ------------------------------------------------------------------------------------------------
+// Every BNF_* variable the library reads for a handle (INTEGRATION.md lists their meaning).  The only other reads are
+// BNF_DEBUG_TN_KIND / BNF_DEBUG_TN_SPLITK, arguments of the one debug call bnf_debug_gemm_tn.
+struct Switches {
+  int ablate = 0;                // BNF_ABLATE (perf experiments, ABLATE builds)
+  int big_tiles = 1;             // BNF_BIG_TILES: 0 = 128 x 128 tiles everywhere, 1 = auto, 2 = 256 x 256 wherever the shape divides
+  int skinny = 1;                // BNF_WGRAD_SKINNY=0: layer-0 weight gradient through the 128 x 128 tiles
+  int tn_ring = 1;               // BNF_TN_RING=0: the two-stage K loop for the 256 x 256 weight-gradient tile
+  int graph_mode = 0;            // BNF_GRAPH=1: replay full-batch MAP steps from a hipGraph
+  bool adam_clear_all = false;   // BNF_ADAM_CLEAR_ALL (presence): no kept gradient range
+  bool vi_sample_pack = true;    // BNF_VI_SAMPLE_PACK=0: k_vi_sample + k_pack_layers instead of the fused sampler
+  bool vi_keep_z = false;        // BNF_VI_KEEP_Z=1: every sample is written to theta_c
+  bool pipeline_set = false;     // BNF_PIPELINE overrides bnf_config.pipeline when set (0 is a value: auto)
+  int pipeline = 0;
+  bool fp8_contract = true;      // BNF_FP8_CONTRACT=0: bf16 W x W contractions in the fp8 handle
+  bool panel_fold0 = true;       // BNF_PANEL_FOLD0=0
+  bool panel_featbwd = true;     // BNF_PANEL_FEATBWD=0
+  bool panel_no_h0l = false;     // BNF_PANEL_NO_H0L (presence)
+  bool overlap = false;          // BNF_OVERLAP=1: weight gradients on a side stream
+  bool wgrad_no_multi = false;   // BNF_WGRAD_NO_MULTI (presence): one launch per W x W layer
+  bool wgrad_order_fwd = false;  // BNF_WGRAD_ORDER=fwd: layer 0 first
+  int ring_splitk = 0;           // BNF_RING_SPLITK: split-K of the un-split ring plan (0 = unset)
+  std::string phase_prof;        // BNF_PHASE_PROF: kernel name ("" = unset)
+};
+
+// lookup: const char*(const char*), getenv in production
+template <typename Lookup>
+inline Switches read_switches(Lookup&& lookup) {
+  Switches s;
+  const char* v;
+  if ((v = lookup("BNF_ABLATE"))) s.ablate = atoi(v);
+  if ((v = lookup("BNF_BIG_TILES"))) s.big_tiles = atoi(v);
+  if ((v = lookup("BNF_WGRAD_SKINNY"))) s.skinny = atoi(v);
+  if ((v = lookup("BNF_TN_RING"))) s.tn_ring = atoi(v);
+  if ((v = lookup("BNF_GRAPH"))) s.graph_mode = atoi(v);
+  s.adam_clear_all = lookup("BNF_ADAM_CLEAR_ALL") != nullptr;
+  if ((v = lookup("BNF_VI_SAMPLE_PACK"))) s.vi_sample_pack = atoi(v) != 0;
+  if ((v = lookup("BNF_VI_KEEP_Z"))) s.vi_keep_z = atoi(v) != 0;
+  if ((v = lookup("BNF_PIPELINE"))) { s.pipeline_set = true; s.pipeline = atoi(v); }
+  if ((v = lookup("BNF_FP8_CONTRACT"))) s.fp8_contract = atoi(v) != 0;
+  if ((v = lookup("BNF_PANEL_FOLD0"))) s.panel_fold0 = atoi(v) != 0;
+  if ((v = lookup("BNF_PANEL_FEATBWD"))) s.panel_featbwd = atoi(v) != 0;
+  s.panel_no_h0l = lookup("BNF_PANEL_NO_H0L") != nullptr;
+  if ((v = lookup("BNF_OVERLAP"))) s.overlap = atoi(v) != 0;
+  s.wgrad_no_multi = lookup("BNF_WGRAD_NO_MULTI") != nullptr;
+  if ((v = lookup("BNF_WGRAD_ORDER"))) s.wgrad_order_fwd = !strcmp(v, "fwd");
+  if ((v = lookup("BNF_RING_SPLITK"))) s.ring_splitk = std::max(1, atoi(v));
+  if ((v = lookup("BNF_PHASE_PROF"))) s.phase_prof = v;
+  return s;
+}
+
+// ---- the weight-gradient plan --------------------------------------------------------------------------------
+enum { WG_TN128 = 0, WG_TN256 = 1, WG_RING = 2, WG_SKINNY = 3 };   // weight-gradient kernels
+// tile sizes the plan counts with (bnf_api.hip asserts them equal to kBM, kBN and kSkRows of bnf_gemm.h)
+constexpr int kPlanBM = 128, kPlanBN = 128, kPlanSkRows = 32;
+
+// what the plan depends on, and nothing else
+struct PlanShape {
+  bool bf16;          // bf16 (or fp8) storage
+  int L, W, F, Fp;    // hidden layers, width the kernels run at, features, padded features
+  int64_t Bp;         // padded batch rows: the contraction depth of the weight gradients
+  int num_cus;
+  bool panel;         // row-panel pipeline
+  bool pad;           // model width < W: gradients pass through a padded copy, nothing is kept
+  int32_t off_kernel[BNF_MAX_LAYERS];   // offsets of the hidden Dense kernels in the parameter vector
+};
+
+// Which kernel computes layer l's weight gradient and with what split-K (1: the kernel STORES dK_l, > 1: f32 atomics).
+struct WgradPlan { int kind, splitk; };
+inline WgradPlan wgrad_plan(const PlanShape& ps, const Switches& sw, int nmem, int l) {
+  const int M = (l == 0) ? ps.F : ps.W, N = ps.W, a_ld = (l == 0) ? ps.Fp : ps.W;
+  const int64_t K = ps.Bp;
+  const int tiles = ((M + kPlanBM - 1) / kPlanBM) * ((N + kPlanBN - 1) / kPlanBN);
+  const int nk = (int)(K / (ps.bf16 ? 64 : 32));
+  const int sk = (1024 + nmem * tiles - 1) / (nmem * tiles);
+  const int base_sk = std::max(1, std::min(sk, std::max(1, nk / 4)));
+  if (ps.bf16 && l == 0 && sw.skinny && a_ld == 64 && N % 512 == 0 && K % 64 == 0) {
+    // layer 0 as a 64 x 512 row stream, one workgroup per CU (144 KiB of LDS): the K split with the shortest
+    // schedule -- rounds of the chip x rows per workgroup (C3/8, 80 members: 3 splits = 240 workgroups in one round
+    // instead of 4 = 320 in two, the second a quarter full); ties go to the fewest splits (fewest atomics)
+    const int64_t base = (int64_t)nmem * (N / 512);
+    const int nks = (int)(K / kPlanSkRows);
+    const int max_s = (int)std::max<int64_t>(1, std::min<int64_t>((ps.num_cus + base - 1) / base, std::max(1, nks / 8)));
+    int best = 1;
+    double best_cost = 1e30;
+    for (int sp = 1; sp <= max_s; ++sp) {
+      const int64_t rounds = (base * sp + ps.num_cus - 1) / ps.num_cus;
+      const double cost = (double)rounds * (double)((nks + sp - 1) / sp);
+      if (cost < best_cost * 0.98) { best_cost = cost; best = sp; }
+    }
+    return {WG_SKINNY, best};
+  }
+  // 256 x 256 tiles when they still fill the chip (members x tiles >= half the CUs)
+  if (sw.big_tiles && M % 256 == 0 && N % 256 == 0) {
+    const int64_t units = (int64_t)nmem * (M / 256) * (N / 256);
+    if (units < 128 && sw.big_tiles != 2 && ps.bf16 && sw.tn_ring && K % 64 == 0 && K >= 16384) {
+      // few large units with a long batch (C5/8: 64 members x one 256 x 256 tile x 71k rows): the ring kernel with K split
+      // until the chip is full -- every operand byte is read ONCE (four 128 x 128 tiles read each half twice), and
+      // the atomics of the splits (256 x 256 floats each) are nothing next to 2 x K x 256 operand elements
+      const int sp = (int)std::min<int64_t>((ps.num_cus + units - 1) / units, K / 4096);
+      if (sp >= 1) return {WG_RING, std::max(1, sp)};
+    }
+    if (units >= 128 || sw.big_tiles == 2) {
+      if (ps.bf16 && sw.tn_ring && K % 64 == 0) {
+        // the four-stage ring, one workgroup per CU, NO split-K: splitting to shorten the last, partly filled
+        // round of workgroups was measured at C3/8 (320 tiles on 256 CUs) -- 2 splits 230 -> 300 us per launch,
+        // 4 splits 438 us, 5,680 -> 5,290 -> 4,730 member-steps/s: the f32 atomics of 80 x 512 x 512 outputs
+        // per split cost far more than the idle quarter round (round-3 measurement).  BNF_RING_SPLITK forces one.
+        return {WG_RING, sw.ring_splitk ? sw.ring_splitk : 1};
+      }
+      return {WG_TN256, base_sk};
+    }
+  }
+  return {WG_TN128, base_sk};
+}
+
+// ---- the step plan -------------------------------------------------------------------------------------------
+constexpr int kWgradMerged = -1;   // StepPlan::launch entry: the W x W layers 1 .. L-1 as ONE launch of the ring kernel
+
+struct StepPlan {
+  WgradPlan layer[BNF_MAX_LAYERS];   // per layer: kernel and split-K
+  bool merged;                       // row-panel pipeline: layers 1 .. L-1 in one launch
+  // the weight-gradient launches of the row-panel pipeline, in order: a layer, or kWgradMerged (the layer kernels'
+  // pipelines start each weight gradient behind its dZ, in the order of their backward chain: n_launch = 0)
+  int n_launch;
+  int launch[BNF_MAX_LAYERS];
+  // gradient ranges [lo, hi) the NEXT step's weight-gradient kernels store, so the optimiser does not clear them.
+  // MAP (k_adam_map takes one range): the first layer l >= 1 with split-K 1, rounded inwards to quads.
+  // VI (k_vi_adam): every layer with split-K 1.
+  int n_keep;
+  int32_t keep_lo[BNF_MAX_LAYERS], keep_hi[BNF_MAX_LAYERS];
+};
+
+// nmem: the members the step's kernels run over (members for MAP, members x samples for VI)
+inline StepPlan make_step_plan(const PlanShape& ps, const Switches& sw, int nmem, bool vi) {
+  StepPlan p{};
+  for (int l = 0; l < ps.L; ++l) p.layer[l] = wgrad_plan(ps, sw, nmem, l);
+
+  // one launch for the W x W layers: all on the un-split ring, and only where it saves rounds of the chip (C3/8: 3 x 320
+  // tiles = 4 rounds instead of 6, +6.6 % on the step; C4/8: 3 x 512 tiles = 6 rounds either way and the merged launch
+  // measured 1 % slower)
+  p.merged = ps.panel && ps.bf16 && ps.L >= 3 && !sw.overlap && !sw.wgrad_no_multi;
+  for (int l = 1; l < ps.L && p.merged; ++l) p.merged = p.layer[l].kind == WG_RING && p.layer[l].splitk == 1;
+  if (p.merged) {
+    const int64_t units = (int64_t)nmem * (ps.W / 256) * (ps.W / 256), cus = ps.num_cus, n = ps.L - 1;
+    p.merged = (n * units + cus - 1) / cus < n * ((units + cus - 1) / cus);
+  }
+
+  // Order: the LAST layer's weight gradient first.  In the panel pipeline every dZ_l exists when these run, and the
+  // panel kernel wrote dZ_0 last: read right away it comes back at two thirds of the HBM rate (dirty lines in the
+  // memory-side cache, profiles/r02w_wgrad_streams.md); after the W x W kernels have streamed their operands it does not.
+  // (BNF_WGRAD_ORDER=fwd: layer 0 first, the order of rounds 1 - 3.)
+  if (ps.panel) {
+    if (p.merged) {
+      p.launch[p.n_launch++] = sw.wgrad_order_fwd ? 0 : kWgradMerged;
+      p.launch[p.n_launch++] = sw.wgrad_order_fwd ? kWgradMerged : 0;
+    } else {
+      for (int i = 0; i < ps.L; ++i) p.launch[p.n_launch++] = sw.wgrad_order_fwd ? i : ps.L - 1 - i;
+    }
+  }
+
+  if (!ps.pad && !sw.adam_clear_all && sw.ablate == 0) {
+    for (int l = vi ? 0 : 1; l < ps.L; ++l) {
+      if (p.layer[l].splitk != 1) continue;
+      const int32_t lo = ps.off_kernel[l], hi = lo + ((l == 0) ? ps.F : ps.W) * ps.W;
+      p.keep_lo[p.n_keep] = vi ? lo : (lo + 3) / 4 * 4;
+      p.keep_hi[p.n_keep] = vi ? hi : hi / 4 * 4;
+      ++p.n_keep;
+      if (!vi) break;
+    }
+  }
+  return p;
+}
+
+}  // namespace bnf

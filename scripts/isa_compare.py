@@ -30,6 +30,7 @@ def kernels(path, mask_kernarg):
         break                                   # (the next function's directives; behind the last kernel the source hash)
       seen_info = seen_info or '.AMDGPU.csdata' in l
       l = re.sub(r'BB\d+_', 'BB_', l)
+      l = re.sub(r'^(\.LBB_\d+:)\s+;', r'\1 ;', l)   # (the comment behind a label is padded to a column: by the masked digits)
       l = re.sub(r'\.L(func_begin|func_end|tmp)\d+', r'.L\1', l)
       l = re.sub(r'\s*; %[\w.]+$', '', l)      # (name of the IR block behind a label: numbered per module)
       if mask_kernarg and re.match(r'^\s+s_load_dword', l):

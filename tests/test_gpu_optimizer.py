@@ -21,7 +21,8 @@ comparison below carries a dtype bar.  `Engine.state` and `Engine.params` are re
 (d) BNF_GRAPH=1 at the one geometry the suite replays (fp32, W 64, depth 2, full batch): the bias corrections and the loss
     column come from device memory.  Other pipelines under capture are not covered.
 
-THE PLANS (wgrad_plan in bnf_api.hip, read for every layer of every case; 3 members, VI: 3 x S virtual members; the
+THE PLANS (asserted on the host, without a GPU, by tests/test_step_plan_host.py)
+(wgrad_plan in bnf_plan.h, read for every layer of every case; 3 members, VI: 3 x S virtual members; the
 default problem has F = 49 features, Fp = 64; K = the padded batch Bp: a multiple of 128, of 256 in the panel pipeline;
 split-K = max(1, (Bp / 32 or 64) / 4) for the 128 x 128 kernel).  "1": the kernel stores, the range may be kept; "> 1":
 f32 atomics into a buffer the optimiser must have cleared.
@@ -228,9 +229,8 @@ def test_probe_spread_is_within_a_third_of_the_bar(case, monkeypatch):
   assert 3 * spread <= _bar(case), (spread, _bar(case))
 
 
-@pytest.mark.parametrize('case', CASES, ids=_ids(CASES))
-def test_frozen_run_state_is_the_closed_form_of_the_probe_gradients(case, monkeypatch):
-  """(a)"""
+def _frozen_run(case, monkeypatch, between_calls=None):
+  """(a); `between_calls` runs after the first call of `train`, when both handles exist."""
   problem = _problem(case)
   model = problem[1]
   eng = _handle(case, problem, monkeypatch, learning_rate=0.0)
@@ -238,7 +238,11 @@ def test_frozen_run_state_is_the_closed_form_of_the_probe_gradients(case, monkey
   theta0 = _init(eng, problem)
   probe.set_params(theta0)
   calls, steps = _steps(case)
-  losses = [eng.train(e0, n) for e0, n in calls]
+  losses = []
+  for i, (e0, n) in enumerate(calls):
+    losses.append(eng.train(e0, n))
+    if i == 0 and between_calls:
+      between_calls()
   torch.cuda.synchronize()
   losses = np.concatenate([l.cpu().numpy() for l in losses], axis=1)
   state, theta = _state(eng), eng.get_params()
@@ -255,6 +259,26 @@ def test_frozen_run_state_is_the_closed_form_of_the_probe_gradients(case, monkey
   want = [R.moments([_grad_blocks(g)[i] for g in grads]) for i in range(k)]
   _check_state(model, state, want, _bar(case), case['name'])
   np.testing.assert_allclose(losses, np.stack(want_loss, axis=1), rtol=LOSS_RTOL)
+
+
+@pytest.mark.parametrize('case', CASES, ids=_ids(CASES))
+def test_frozen_run_state_is_the_closed_form_of_the_probe_gradients(case, monkeypatch):
+  """(a)"""
+  _frozen_run(case, monkeypatch)
+
+
+RING_CASE = next(c for c in CASES if c['env'] == (('BNF_BIG_TILES', '2'),))   # 6: the smallest geometry with a kept RING x1 range
+
+
+def test_kept_range_survives_an_environment_change(monkeypatch):
+  """(a) at case 6 with BNF_RING_SPLITK=2 appearing in the environment between the two calls of `train`, after both
+  handles exist.  The plan belongs to the handle (bnf_plan.h, made at bnf_create): the steps of the second call launch
+  the kernels the first call's optimiser left the L1 range uncleared for.  An engine that derived the plan from the
+  live environment at every step would launch RING x2 -- f32 atomics -- into the range the last step of the first call
+  kept: the stale gradient is accumulated into.  Confirmed once on a build of the commit before the plan became handle
+  state: Dense_1/kernel off by 3.6e-2 of the leaf's max in m and 5.2e-2 in v (one step's gradient counted twice among
+  five; the bar is 1e-4), every other leaf within the bar."""
+  _frozen_run(RING_CASE, monkeypatch, between_calls=lambda: monkeypatch.setenv('BNF_RING_SPLITK', '2'))
 
 
 def _check_update(model, theta, new_theta, m, v, t, what):

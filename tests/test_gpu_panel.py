@@ -438,3 +438,40 @@ def test_bias_and_output_kernel_gradients_keep_explicit_bars(width, depth, n_row
     errs = _leaf_errs(model, res['panel'], ref)
     bad = {k: errs[k] for k in leaves if errs[k] > bar}
     assert not bad, (ref_name, bad)
+
+
+def test_switches_belong_to_the_handle(monkeypatch):
+  """Every engine switch is read once, at bnf_create, and belongs to the handle from then on (bnf_plan.h).  The
+  smallest geometry with the RING plan and the merged launch (case 6 of tests/test_gpu_optimizer.py): handle A is
+  created under BNF_BIG_TILES=2, handle B with BNF_WGRAD_NO_MULTI=1 as well, and the variable is gone again before
+  either trains.  A launches the W x W weight gradients of its two layers >= 1 merged, one launch per step; B one
+  launch per layer, two per step -- also in later calls of `train`.  Same kernels on the same operands, merged or not:
+  the losses agree at the project's bar for two evaluations of one step (LOSS_RTOL of tests/test_gpu_optimizer.py)."""
+  LOSS_RTOL = 1e-5
+  net, model, X, y = util.make_problem(n_rows=300, width=256, depth=3)
+  E = 3
+  theta = util.random_theta(model, E, scale=0.3)
+  kw = dict(members=E, seed=7, learning_rate=0.005, compute_dtype='bf16', pipeline='panel')
+  monkeypatch.setenv('BNF_BIG_TILES', '2')
+  monkeypatch.delenv('BNF_WGRAD_NO_MULTI', raising=False)
+  a = _engine(net, X, y, **kw)
+  monkeypatch.setenv('BNF_WGRAD_NO_MULTI', '1')
+  b = _engine(net, X, y, **kw)
+  monkeypatch.delenv('BNF_WGRAD_NO_MULTI')
+  losses = {}
+  for name, eng in (('a', a), ('b', b)):
+    eng.set_params(theta)
+    eng.profile('gemm_wgrad')
+    losses[name] = [eng.train(0, 2)]
+  torch.cuda.synchronize()
+  assert a.profile_read()['gemm_wgrad']['calls'] == 2      # 2 steps x 1 merged launch
+  assert b.profile_read()['gemm_wgrad']['calls'] == 4      # 2 steps x 2 layers
+  for name, eng in (('a', a), ('b', b)):
+    losses[name].append(eng.train(2, 2))
+  torch.cuda.synchronize()
+  assert a.profile_read()['gemm_wgrad']['calls'] == 2 + 2  # the counts accumulate: the same rate for two further steps
+  assert b.profile_read()['gemm_wgrad']['calls'] == 4 + 4
+  la, lb = (np.concatenate([l.cpu().numpy() for l in losses[k]], axis=1) for k in ('a', 'b'))
+  a.close(); b.close()
+  assert la.shape == (E, 4) and np.all(np.isfinite(la))
+  np.testing.assert_allclose(la, lb, rtol=LOSS_RTOL)
