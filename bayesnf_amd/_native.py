@@ -69,7 +69,7 @@ EXPORTS = (
     'bnf_count_mixture_quantiles_weighted', 'bnf_predictive_scores_weighted', 'bnf_count_rps_weighted',
     'bnf_predictive_group_extremes', 'bnf_sample_pair_moments', 'bnf_predictive_group_episodes',
     'bnf_sample_ranks', 'bnf_rank_probabilities', 'bnf_predictive_group_cumulative', 'bnf_predictive_group_windows',
-    'bnf_debug_loss_and_grad',
+    'bnf_predictive_combinations', 'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
     'bnf_kernel_flops', 'bnf_comm_available', 'bnf_comm_unique_id', 'bnf_comm_create', 'bnf_allgather',
@@ -169,6 +169,8 @@ def load():
                                                   vp, vp, vp, vp, vp]
   lib.bnf_predictive_group_windows.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, i32, vp,
                                                vp, vp, vp, vp, vp, vp]
+  lib.bnf_predictive_combinations.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp,
+                                              C.c_size_t, vp]
   lib.bnf_predictive_scores.argtypes = [vp, vp, vp, i64, i64, vp, vp, C.c_size_t, vp, vp, vp, vp]
   lib.bnf_count_rps.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_sample_summaries.argtypes = [vp, vp, i64, i64, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]

@@ -34,6 +34,7 @@
 #include "bnf_panel.h"
 #include "bnf_gemm8.h"
 #include "bnf_sampling.h"
+#include "bnf_combinations.h"
 #include "bnf_extremes.h"
 #include "bnf_episodes.h"
 #include "bnf_cumulative.h"
@@ -2035,6 +2036,40 @@ int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const fl
   if (const int rc = no_device()) return rc;
   return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
                                     sample0, cum_weights, work, work_bytes, out);
+}
+
+// ---- linear combinations of the rows of the sample paths (bnf_combinations.h) ----
+// The position count nnz = form_offsets[n_forms] sizes the grid and the work buffer and lives on the device: it is read
+// back (4 bytes) after everything that can be refused without it has been.
+int bnf_predictive_combinations(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                const int32_t* form_offsets, const int32_t* form_rows, const double* form_coef,
+                                int64_t n_forms, int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                const double* cum_weights, void* work, size_t work_bytes, double* out) {
+  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
+  if (!form_offsets || !form_rows || !form_coef || !work || !out || n_forms < 1 || n_forms > 0x7ffffffeLL)
+    return fail(BNF_ERR_INVALID, "argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  int32_t nnz32 = -1;
+  HIPCHK(hipMemcpyAsync(&nnz32, form_offsets + n_forms, sizeof(nnz32), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int64_t nnz = nnz32;
+  if (nnz < 0) return fail(BNF_ERR_INVALID, "form_offsets[n_forms] = %lld: the position count must be in [0, 2^31)", (long long)nnz);
+  int64_t chunk = n_samples;
+  if (nnz > 0)
+    if (const int rc = group_chunk(nnz, n_samples, 2 * sizeof(double), work_bytes, &chunk)) return rc;
+  HIPCHK(hipMemsetAsync(out, 0, (size_t)n_samples * (size_t)n_forms * sizeof(double), h->stream));   // EMPTY forms
+  if (nnz > 0)
+    group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
+      const dim3 grid = pred_grid(nnz, kPredTile, n);
+      double* partial = (double*)work, *o = out + s0 * n_forms;
+      hipLaunchKernelGGL((k_predictive_combinations<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
+                         (int32_t)n_members, n_rows, nnz, form_offsets, form_rows, form_coef, (int32_t)n_forms, n, seed,
+                         row0, sample0 + s0, cum_weights, partial, o);
+      hipLaunchKernelGGL(k_predictive_group_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, form_offsets,
+                         (int32_t)n_forms, nnz, n, partial, o);
+    });
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
 }
 
 // ---- group peaks and threshold exceedances of the sample paths (bnf_extremes.h) ----

@@ -369,6 +369,45 @@ class Engine:
     torch.cuda.synchronize(self.device)     # `work`, `off` and `rows` are released on return
     return out
 
+  def predictive_combinations(self, loc: torch.Tensor, aux: torch.Tensor, form_offsets, form_rows, form_coef,
+                              n_samples: int, seed, row0=0, sample0=0, cum_weights=None) -> torch.Tensor:
+    """Linear combinations of the rows of the same sample paths (include/bnf.h bnf_predictive_combinations) ->
+    (n_samples, K) f64 on the device, without materialising the draws: out[s][k] = sum_p form_coef[p] * draw(s,
+    form_rows[p]) over the positions of form k.  form_offsets (K + 1) int32, form_rows (nnz) int32, form_coef (nnz) f64:
+    a CSR over positions (`inference.combinations_csr`); a row may occur at many positions or at none, an empty form is
+    0.  Deterministic: the same call gives the same bits; forms that partition the rows with coefficients 1 give the bits
+    of `predictive_group_sums`.  cum_weights as for `predictive_samples`; None: equal weights."""
+    loc = loc.contiguous().float()
+    aux = aux.contiguous().float()
+    M, R = loc.shape
+    as_i32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+                        ).to(self.device, dtype=torch.int32).contiguous()
+    off, rows = as_i32(form_offsets), as_i32(form_rows)
+    coef = self._as_f64(form_coef, None, 'form_coef')
+    K, nnz = off.numel() - 1, rows.numel()
+    if K < 1 or off.dim() != 1 or rows.dim() != 1 or tuple(coef.shape) != (nnz,):
+      raise ValueError(f'form_offsets needs >= 2 entries and form_rows, form_coef one entry per position; got '
+                       f'{tuple(off.shape)}, {tuple(rows.shape)}, {tuple(coef.shape)}')
+    # the library takes the position count from form_offsets: it must be the arrays' length (read on the host when the
+    # offsets arrive there, else 4 bytes back from the device)
+    end = int(off[-1].item()) if isinstance(form_offsets, torch.Tensor) else int(np.asarray(form_offsets).reshape(-1)[-1])
+    if end != nnz:
+      raise ValueError(f'form_offsets ends at {end}; form_rows and form_coef hold {nnz} positions')
+    n_samples = int(n_samples)
+    out = torch.empty((n_samples, K), dtype=torch.float64, device=self.device)
+    # per-tile partial sums: two doubles per tile of positions and path.  Arrays without a position have no device
+    # address: one spare entry keeps every pointer the library checks non-NULL.
+    work = self._group_work(16, max(nnz, 1), n_samples)
+    if nnz == 0:
+      rows, coef = rows.new_zeros(1), coef.new_zeros(1)
+    cum = self._cum(cum_weights, M)
+    _native.check(self.lib.bnf_predictive_combinations(
+        self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(off), _ptr(rows), _ptr(coef), K, n_samples,
+        C.c_uint64(_native.seed_to_u64(seed)), int(row0), int(sample0), _ptr(cum), _ptr(work),
+        C.c_size_t(work.numel()), _ptr(out)), 'bnf_predictive_combinations')
+    torch.cuda.synchronize(self.device)     # `work`, `off`, `rows`, `coef` and `cum` are released on return
+    return out
+
   def _group_inputs(self, loc, aux, seg_offsets, seg_rows):
     """The inputs the group reductions share, normalised -> (loc (M, R) f32, aux f32, seg_offsets (G + 1,) int32,
     seg_rows (R,) int32, M, R, G), all contiguous on the device."""

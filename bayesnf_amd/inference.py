@@ -22,6 +22,7 @@ import warnings
 from typing import Any
 
 import numpy as np
+import pandas as pd
 import torch
 
 from . import _native
@@ -507,6 +508,126 @@ def total_summaries(features, observation_model, params, model_args, num_samples
     out = {k: v.cpu().numpy() for k, v in res.items()}
     if y is not None and energy:
       out['energy_score'] = eng.sample_energy_score(totals, y)
+    return out
+
+
+_COMBINATION_MAX_POSITIONS = (1 << 31) - 1     # nnz of bnf_predictive_combinations: the CSR offsets are int32
+
+
+def combinations_csr(spec, n_rows, names=None):
+  """Linear combinations of the rows of a sample path as CSR over positions -> (keys, form_offsets (K + 1,) int32,
+  form_rows (nnz,) int32, form_coef (nnz,) float64), the layout `bnf_predictive_combinations` takes (include/bnf.h):
+  combination k is sum_p form_coef[p] * x[form_rows[p]] over its positions form_offsets[k] <= p < form_offsets[k + 1].
+  `spec` is one of
+    a dict name -> (n_rows,) coefficients           keys = pd.Index of the names, in the dict's order
+    a dense (K, n_rows) array (not a tuple)         keys = RangeIndex(K), or `names`
+    a tuple (form, row, coef) of equal-length 1-d arrays (COO)
+                                                    K = len(names) if given, else max(form) + 1; keys as for dense
+  Coefficients equal to 0 are dropped; the positions are sorted by form, then by row; a combination left without a
+  position stays, as an empty form (its value is 0).  A row may occur in many combinations or in none.
+  ValueError for non-finite coefficients, rows outside [0, n_rows), negative form indices (or ones >= len(names)), a
+  repeated (form, row) pair in a COO triple, 2^31 positions or more, and shapes that do not fit."""
+  n_rows = int(n_rows)
+  if n_rows < 1:
+    raise ValueError(f'n_rows={n_rows}: need at least one row')
+
+  def numbers_of(a, what, dtype=np.float64):
+    try:
+      return np.asarray(a, dtype=dtype)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'combinations: {what} must be an array of numbers') from e
+
+  def integers_of(a, what):
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+      raise ValueError(f'combinations: {what} must be a 1-d integer array')
+    return a.astype(np.int64)
+
+  if isinstance(spec, dict):
+    if names is not None:
+      raise ValueError('combinations: a dict names its combinations itself; names must be None')
+    if not spec:
+      raise ValueError('combinations: need at least one combination')
+    names = list(spec.keys())
+    rows_of = [numbers_of(v, f'the coefficients of {k!r}') for k, v in spec.items()]
+    bad = [k for k, v in zip(names, rows_of) if v.shape != (n_rows,)]
+    if bad:
+      raise ValueError(f'combinations: {bad[0]!r} must hold one coefficient per row ({n_rows},)')
+    spec = np.stack(rows_of)
+  if isinstance(spec, tuple):
+    if len(spec) != 3:
+      raise ValueError('combinations: a tuple must be the COO triple (form, row, coef)')
+    form, row = integers_of(spec[0], 'form'), integers_of(spec[1], 'row')
+    coef = numbers_of(spec[2], 'coef')
+    if coef.ndim != 1 or not form.shape == row.shape == coef.shape:
+      raise ValueError(f'combinations: form, row and coef must be 1-d arrays of one length; got {form.shape}, '
+                       f'{row.shape}, {coef.shape}')
+    if form.size and form.min() < 0:
+      raise ValueError('combinations: negative form index')
+    K = len(names) if names is not None else (int(form.max()) + 1 if form.size else 0)
+    if K < 1:
+      raise ValueError('combinations: need at least one combination')
+    if form.size and form.max() >= K:
+      raise ValueError(f'combinations: form index {int(form.max())} with {K} names')
+    if row.size and (row.min() < 0 or row.max() >= n_rows):
+      raise ValueError(f'combinations: rows must lie in [0, {n_rows})')
+    if not np.all(np.isfinite(coef)):
+      raise ValueError('combinations: coefficients must be finite')
+    cell = form * n_rows + row
+    order = np.argsort(cell, kind='stable')                 # by form, then by row
+    cell = cell[order]
+    if cell.size > 1 and np.any(cell[1:] == cell[:-1]):
+      raise ValueError('combinations: a (form, row) pair is repeated in the COO triple')
+    keep = order[coef[order] != 0]
+    form, row, coef = form[keep], row[keep], coef[keep]
+  else:
+    dense = numbers_of(spec, 'a dense spec')
+    if dense.ndim != 2 or dense.shape[0] < 1 or dense.shape[1] != n_rows:
+      raise ValueError(f'combinations: a dense spec must be (K, {n_rows}) with K >= 1; got {dense.shape}')
+    if not np.all(np.isfinite(dense)):
+      raise ValueError('combinations: coefficients must be finite')
+    K = dense.shape[0]
+    if names is not None and len(names) != K:
+      raise ValueError(f'combinations: {len(names)} names for {K} combinations')
+    form, row = np.nonzero(dense)                            # row-major: by form, then by row
+    coef = dense[form, row]
+  if form.size > _COMBINATION_MAX_POSITIONS:
+    raise ValueError(f'combinations: {form.size} positions; at most {_COMBINATION_MAX_POSITIONS}')
+  keys = pd.RangeIndex(K) if names is None else pd.Index(names)
+  form_offsets = np.zeros(K + 1, dtype=np.int64)
+  np.cumsum(np.bincount(form, minlength=K), out=form_offsets[1:])
+  return (keys, form_offsets.astype(np.int32), np.ascontiguousarray(row, dtype=np.int32),
+          np.ascontiguousarray(coef, dtype=np.float64))
+
+
+def combination_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, combinations,
+                          observed=None, quantiles=(), energy=True, samples=False, compute_dtype=None, weights=None):
+  """Linear combinations of the rows of the joint sample paths -- weighted means, contrasts, overlapping groups --
+  summarised and scored on the GPU: the (num_samples, K) matrix out[s][k] = sum_p coef[p] * draw(s, rows[p]) is formed
+  without materialising the draws (include/bnf.h bnf_predictive_combinations), stays on the device and only the summaries
+  come back (bnf_sample_summaries, bnf_sample_energy_score).  combinations = (form_offsets, form_rows, form_coef) as
+  `combinations_csr` builds them; observed (K,) the observed values, NaN where a combination is not to be scored.
+  -> the dict of `total_summaries` ('mean', 'quantiles', with `observed` 'crps', 'pit' and 'energy_score'), and with
+  samples=True also 'samples' (num_samples, K) float64, the matrix itself.
+  The caps of `total_summaries` apply: num_samples <= 16,384 and num_samples * K <= 2^28 cells, ValueError beyond.  A row
+  that occurs at m positions is drawn m times.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = _num_samples(num_samples, 'combinations')
+  levels = _quantile_levels(quantiles)
+  form_offsets, form_rows, form_coef = combinations
+  n_forms = len(form_offsets) - 1
+  _check_cells(num_samples, n_forms, 'matrix of combinations is')
+  observed = _per_group('observed', 'value', observed, n_forms)
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    x = eng.predictive_combinations(loc, aux, form_offsets, form_rows, form_coef, num_samples, seed64, **kw)
+    y = None if observed is None else torch.from_numpy(observed).to(eng.device)
+    res = eng.sample_summaries(x, y, levels)
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    if y is not None and energy:
+      out['energy_score'] = eng.sample_energy_score(x, y)
+    if samples:
+      out['samples'] = x.cpu().numpy()
     return out
 
 

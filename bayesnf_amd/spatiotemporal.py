@@ -218,6 +218,75 @@ def group_rows_ordered(table, group_by, order_by):
   return keys, seg_offsets, seg_rows
 
 
+def group_combinations(table, group_by, weight=None, mean=False):
+  """One linear combination of the rows per group of `group_by` (the grouping of `group_rows`) -> (keys, (form, row,
+  coef)): `keys` the sorted Index of the groups, and a COO triple `inference.combinations_csr` and
+  `predict_combinations` take.  The coefficient of a row is 1, or its `weight`: a column name or one finite value per row
+  (an area, a population).  mean=True divides by the group's sum of coefficients: the (weighted) mean of the group
+  instead of its (weighted) total; a group whose weights sum to 0 is a ValueError."""
+  keys, seg_offsets, seg_rows = group_rows(table, group_by)
+  row = seg_rows.astype(np.int64)
+  form = np.repeat(np.arange(len(keys), dtype=np.int64), np.diff(seg_offsets.astype(np.int64)))
+  if weight is None:
+    coef = np.ones(len(row), dtype=np.float64)
+  else:
+    if isinstance(weight, str):
+      if weight not in table.columns:
+        raise ValueError(f'weight: {weight!r} is not among the columns of the table')
+      weight = table[weight].values
+    try:
+      w = np.asarray(weight, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError('weight must be a column name or one number per row of the table') from e
+    if w.shape != (len(table),):
+      raise ValueError(f'weight must hold one value per row ({len(table)},); got {w.shape}')
+    if not np.all(np.isfinite(w)):
+      raise ValueError('weight must be finite')
+    coef = w[row]
+  if mean:
+    total = np.add.reduceat(coef, seg_offsets[:-1].astype(np.int64))      # group_rows makes no empty group
+    if np.any(total == 0):
+      raise ValueError(f'mean=True: the weights of group {keys[int(np.flatnonzero(total == 0)[0])]!r} sum to 0')
+    coef = coef / total[form]
+  return keys, (form, row, coef)
+
+
+def stack_combinations(*parts):
+  """Several (keys, (form, row, coef)) results of `group_combinations` joined into one: the keys concatenated in the
+  order given, the form indices shifted to match.  How a hierarchy is written -- places, regions and the whole table as
+  combinations of the same sample paths: stack_combinations(group_combinations(t, 'place'), group_combinations(t,
+  'region'), ...)."""
+  if not parts:
+    raise ValueError('stack_combinations: nothing to stack')
+  labels, forms, rows, coefs, base = [], [], [], [], 0
+  for part in parts:
+    try:
+      keys, (form, row, coef) = part
+    except (TypeError, ValueError) as e:
+      raise ValueError('stack_combinations: every part is (keys, (form, row, coef))') from e
+    labels.extend(list(keys))
+    forms.append(np.asarray(form, dtype=np.int64) + base)
+    rows.append(np.asarray(row, dtype=np.int64))
+    coefs.append(np.asarray(coef, dtype=np.float64))
+    base += len(keys)
+  keys = pd.Index(labels, tupleize_cols=False)
+  return keys, (np.concatenate(forms), np.concatenate(rows), np.concatenate(coefs))
+
+
+def combination_target_sums(target, form_offsets, form_rows, form_coef):
+  """Observed combinations: the float64 sum of coef * target over the positions of every form of the CSR layout
+  `inference.combinations_csr` returns -> (K,); NaN for a form with a NaN target among its positions, 0 for an empty
+  form.  Rows whose coefficient is 0 hold no position and do not count."""
+  target = np.asarray(target, dtype=np.float64)
+  form_offsets = np.asarray(form_offsets, dtype=np.int64)
+  term = np.asarray(form_coef, dtype=np.float64) * target[np.asarray(form_rows, dtype=np.int64)]
+  out = np.zeros(len(form_offsets) - 1)
+  full = np.diff(form_offsets) > 0
+  if term.size:
+    out[full] = np.add.reduceat(term, form_offsets[:-1][full])
+  return out
+
+
 def group_target_sums(target, seg_offsets, seg_rows):
   """Observed totals: the float64 sum of `target` (R,) over the rows of every group of the CSR layout `group_rows`
   returns -> (G,); NaN for a group with a NaN target among its rows (and for an empty one, which `group_rows` never makes)."""
@@ -596,8 +665,8 @@ class BayesianNeuralFieldEstimator:
     def run(fn, **particular):
       rows = self.data_handler.get_test(table)
       return fn(rows, self.observation_model, self.params_, self._model_args(rows.shape), int(num_samples), seed,
-                ensemble_dims=self._ensemble_dims, groups=None if keys is None else (seg_offsets, seg_rows),
-                compute_dtype=self.compute_dtype, **particular, **kw)
+                ensemble_dims=self._ensemble_dims, compute_dtype=self.compute_dtype,
+                **({} if keys is None else {'groups': (seg_offsets, seg_rows)}), **particular, **kw)
 
     return types.SimpleNamespace(y=y, thr=thr, keys=keys, seg_offsets=seg_offsets, seg_rows=seg_rows, run=run)
 
@@ -663,7 +732,8 @@ class BayesianNeuralFieldEstimator:
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
     `predict_episodes`, `score_episodes`, `predict_cumulative`, `score_cumulative`, `predict_windows`, `score_windows`,
-    `predict_dependence`, `score_dependence`, `predict_ranking` and `score_ranking`
+    `predict_dependence`, `score_dependence`, `predict_ranking`, `score_ranking`, `predict_combinations` and
+    `score_combinations`
     (weights=...) and scored on another table by `weighted_log_density`; they are taken by the marginal forecast as well:
     `predict` and `score` (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.
     `fit` is unchanged."""
@@ -760,6 +830,65 @@ class BayesianNeuralFieldEstimator:
     out = f.run(inference.total_summaries, observed=observed, quantiles=tuple(quantiles), energy=bool(energy))
     scored = ~np.isnan(observed)
     out.update(keys=f.keys, observed=observed, n=int(scored.sum()))
+    out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')
+    return out
+
+  def _combination_summaries(self, what, table, combinations, quantiles, num_samples, seed, weights, samples=False,
+                             target=False, energy=False):
+    """The shared front (`_paths` without a grouping), then the spec -> CSR, the observed combinations for a score, and the
+    call.  -> (keys, observed or None, dict of `inference.combination_summaries`)."""
+    f = self._paths(what, table, None, num_samples, seed, weights, noun='combinations', target=target)
+    names = None
+    if (isinstance(combinations, tuple) and len(combinations) == 2 and isinstance(combinations[1], tuple)
+        and len(combinations[1]) == 3):                       # what group_combinations / stack_combinations return
+      names, combinations = combinations
+    try:
+      keys, off, rows, coef = inference.combinations_csr(combinations, len(table), names=names)
+    except ValueError as e:
+      raise ValueError(f'{what}: {e}') from e
+    if int(num_samples) * len(keys) > inference._TOTALS_MAX_CELLS:
+      raise ValueError(f'{what}: {num_samples} sample paths x {len(keys)} combinations: at most '
+                       f'{inference._TOTALS_MAX_CELLS} cells')
+    observed = combination_target_sums(f.y, off, rows, coef) if target else None
+    out = f.run(inference.combination_summaries, combinations=(off, rows, coef), observed=observed, quantiles=tuple(quantiles), energy=bool(energy),
+                samples=bool(samples))
+    return keys, observed, out
+
+  def predict_combinations(self, table, combinations, quantiles=(0.5,), num_samples=1000, seed=0, weights=None,
+                           samples=False):
+    """Mean and quantile bands of LINEAR COMBINATIONS of the rows of the sample paths of `predict_samples(table,
+    num_samples, seed)`: weighted means (the population-weighted mean of a region, incidence per 100k), contrasts (this
+    week minus last week, place A minus place B) and overlapping groups (a row in its county, its state and the nation),
+    all in the same paths, formed and summarised on the GPU.  `combinations` is
+      a dict name -> one coefficient per row of `table`, a dense (K, len(table)) array, or a COO tuple (form, row, coef)
+      (`inference.combinations_csr`), or
+      what `group_combinations` / `stack_combinations` return: (keys, (form, row, coef)).
+    A row may occur in many combinations or in none; coefficients of 0 are dropped.  -> dict:
+      'keys'       the combinations: the dict's names, the keys given, or a RangeIndex
+      'mean' (K,)  'quantiles' (len(quantiles), K)   numpy's default 'linear' quantile of the sampled values
+      'samples'    samples=True: (num_samples, K) float64, the sampled values themselves; equal to
+                   predict_samples(table, num_samples, seed) @ coefficients.T up to float64 rounding
+    num_samples <= 16,384 and num_samples * K <= 2^28.  A row named by m combinations is drawn m times.
+    weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    keys, _, out = self._combination_summaries('predict_combinations', table, combinations, quantiles, num_samples, seed,
+                                               weights, samples=samples)
+    out['keys'] = keys
+    return out
+
+  def score_combinations(self, table, combinations, quantiles=(0.025, 0.5, 0.975), num_samples=1000, seed=0, energy=True,
+                         weights=None):
+    """The forecast of `predict_combinations(table, combinations, ...)` scored against the same combinations of the
+    observations `table[target_col]`, on the GPU.  -> the dict of `predict_combinations` (with 'samples' left out) plus
+      'observed'      (K,) sum of coefficient x target over the combination's rows; NaN when any of them has a NaN
+                      target (rows with coefficient 0 do not count): such a combination is not scored
+      'crps'          (K,) ensemble CRPS of every combination; NaN where not scored       'pit'  (2, K) as in `score_totals`
+      'n'             number of combinations scored       'mean_crps'  mean of 'crps' over them
+      'energy_score'  energy=True: the energy score of the joint paths over the scored combinations
+    The target checks are those of `score_totals`."""
+    keys, observed, out = self._combination_summaries('score_combinations', table, combinations, quantiles, num_samples,
+                                                      seed, weights, target=True, energy=energy)
+    scored = ~np.isnan(observed)
+    out.update(keys=keys, observed=observed, n=int(scored.sum()))
     out['mean_crps'] = float(np.mean(out['crps'][scored], dtype=np.float64)) if scored.any() else float('nan')
     return out
 

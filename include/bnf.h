@@ -324,6 +324,40 @@ int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const fl
                                        int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
                                        const double* cum_weights, void* work, size_t work_bytes, double* out);
 
+/* LINEAR COMBINATIONS of the rows of the same sample paths, without materialising the draws: weighted means, contrasts
+ * (this week minus last week) and overlapping groups (a row in its county, its state and the nation) in the same paths.
+ * The reference has no counterpart (it would multiply `.sample()` by a matrix on the host).  loc, aux, row0, sample0 and
+ * cum_weights (NULL = equal weights) as for bnf_predictive_group_sums_weighted.
+ *   form_offsets DEVICE int32 (n_forms + 1), form_rows DEVICE int32 (nnz), form_coef DEVICE f64 (nnz): a CSR over
+ *     POSITIONS; form k owns the positions form_offsets[k] .. form_offsets[k + 1] - 1.  [0] = 0, nondecreasing,
+ *     nnz = form_offsets[n_forms], 0 <= nnz < 2^31.  The call reads nnz back from the device (4 bytes), after the checks
+ *     below.
+ *   out DEVICE (n_samples, n_forms) f64
+ * COEFFICIENT: out[s][k] = the f64 sum over the positions p of form k of form_coef[p] * (double)x, x the f32 that
+ *   bnf_predictive_samples writes for (seed, sample0 + s, row0 + form_rows[p]), bit for bit.  Each product is one f64
+ *   multiply, rounded once and never contracted into the addition that follows.
+ * OVERLAP: a row may stand at any number of positions, of the same form or of different ones; every occurrence adds, and
+ *   the draw is the same at each (a row at m positions is drawn m times).  A row at no position is never drawn.  A
+ *   position whose row lies outside [0, n_rows) adds nothing, whatever its coefficient.
+ * EMPTY: a form without positions is 0.0.
+ * NaN: a NaN coefficient or a NaN draw makes the value of its own form NaN, and of no other form.
+ * DETERMINISM: no floating-point atomics.  The position axis is cut into tiles of BNF_GROUP_TILE and the order of every
+ *   sum depends only on form_offsets: two calls give the same bits, and neither sample0 chunking nor the number of passes
+ *   that work_bytes forces changes them.  row0 is the global index of loc's first column; the ROW axis cannot be cut
+ *   into chunks here, because a form may span all rows: loc holds every row a form names.  When the forms are a
+ *   partition of the rows (nnz = n_rows, every row once) and every coefficient is 1.0, out has the bits of
+ *   bnf_predictive_group_sums (with cum_weights: of bnf_predictive_group_sums_weighted) for that grouping.
+ *   work DEVICE, work_bytes: per-tile partial sums, 16 bytes x ceil(nnz / BNF_GROUP_TILE) per sample path; the samples
+ *     are processed in as many passes as the buffer asks for
+ * BNF_ERR_INVALID, with nothing launched: n_members, n_rows, n_forms or n_samples < 1, a NULL loc, aux, form_offsets,
+ *   form_rows, form_coef, work or out, row0 / sample0 out of range, a negative position count, and a work buffer below one
+ *   path's worth.  An unbound handle is BNF_ERR_STATE, as for bnf_predictive_group_sums.
+ * Runs on the handle's stream, does not touch the training state, works on forward-only handles. */
+int bnf_predictive_combinations(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
+                                const int32_t* form_offsets, const int32_t* form_rows, const double* form_coef,
+                                int64_t n_forms, int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
+                                const double* cum_weights /* may be NULL */, void* work, size_t work_bytes, double* out);
+
 /* PEAKS and threshold EXCEEDANCES of the same sample paths over groups of rows, without materialising the draws (the
  * reference has no counterpart: it would reduce `.sample()` on the host).  The value at (path s, row r) is the f32 that
  * bnf_predictive_samples writes for (seed, sample0 + s, row0 + r), bit for bit; loc, aux, seg_offsets, seg_rows, row0,
