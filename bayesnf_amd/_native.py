@@ -30,6 +30,9 @@ PAIR_COL_TILE, PAIR_PATH_CHUNK, PAIR_MATRIX_MAX_COLS = 64, 32, 4096
 # BNF_RANK_*: most columns of bnf_sample_ranks (a path's values are sorted in LDS); paths per LDS chunk and most cells
 # (top_k * n_cols) of bnf_rank_probabilities
 RANK_MAX_COLS, RANK_PATH_CHUNK, RANK_MAX_CELLS = 16384, 32, 1 << 24
+# BNF_DEPTH_NONE / BNF_BAND_MAX_LEVELS: the pre-fill of the depth matrices of bnf_sample_depths; most coverage levels /
+# queried bands per call of bnf_depth_levels and most levels of bnf_sample_envelope
+DEPTH_NONE, BAND_MAX_LEVELS = 0x7fffffff, 64
 GROUP_TILE = 1024   # BNF_GROUP_TILE: rows per partial sum of bnf_predictive_group_sums (sizes its work buffer)
 EXTREMES_WORK_PER_TILE = 32   # BNF_EXTREMES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_extremes' work buffer
 EPISODES_WORK_PER_TILE = 80   # BNF_EPISODES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_episodes' work buffer
@@ -69,7 +72,8 @@ EXPORTS = (
     'bnf_count_mixture_quantiles_weighted', 'bnf_predictive_scores_weighted', 'bnf_count_rps_weighted',
     'bnf_predictive_group_extremes', 'bnf_sample_pair_moments', 'bnf_predictive_group_episodes',
     'bnf_sample_ranks', 'bnf_rank_probabilities', 'bnf_predictive_group_cumulative', 'bnf_predictive_group_windows',
-    'bnf_predictive_combinations', 'bnf_debug_loss_and_grad',
+    'bnf_predictive_combinations', 'bnf_sample_depths', 'bnf_depth_levels', 'bnf_sample_envelope',
+    'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
     'bnf_kernel_flops', 'bnf_comm_available', 'bnf_comm_unique_id', 'bnf_comm_create', 'bnf_allgather',
@@ -178,6 +182,10 @@ def load():
   lib.bnf_sample_pair_moments.argtypes = [vp, vp, i64, i64, C.c_double, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
   lib.bnf_sample_ranks.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
   lib.bnf_rank_probabilities.argtypes = [vp, vp, vp, i64, i64, i32, vp]
+  lib.bnf_sample_depths.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, vp]
+  lib.bnf_depth_levels.argtypes = [vp, vp, i64, i64, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, vp, vp, vp, vp,
+                                   vp]
+  lib.bnf_sample_envelope.argtypes = [vp, vp, i64, i64, vp, vp, i32, i64, vp, vp]
   lib.bnf_member_log_density.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_stacking_weights.argtypes = [vp, vp, i64, i64, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
   lib.bnf_predictive_samples_weighted.argtypes = [vp, vp, vp, i64, i64, i64, C.c_uint64, i64, i64, vp, vp]

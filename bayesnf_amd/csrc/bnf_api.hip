@@ -44,6 +44,7 @@
 #include "bnf_totals.h"
 #include "bnf_dependence.h"
 #include "bnf_ranking.h"
+#include "bnf_bands.h"
 #include "bnf_stacking.h"
 #include "bnf_plan.h"
 
@@ -2513,6 +2514,92 @@ int bnf_rank_probabilities(bnf_handle* h, const int32_t* above, const int32_t* t
   HIPCHK(hipSetDevice(h->cfg.device));
   hipLaunchKernelGGL(k_rank_probabilities, dim3(cdiv(n_cols, kRankSlab), cdiv(top_k, kRankKPerBlock)), dim3(256), 0,
                      h->stream, above, ties, n_samples, n_cols, top_k, out);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- simultaneous bands of sample paths: depths, levels, envelopes (bnf_bands.h) --------
+struct BandSlab { int P, W, threads; };
+static BandSlab band_slab(int64_t S) {
+  BandSlab b;
+  b.P = 1;
+  while (b.P < S) b.P <<= 1;
+  b.W = std::min(kSumMaxCols, kSumMaxSamples / b.P);
+  b.threads = std::min(1024, std::max(64, b.W * b.P / 2));          // a multiple of 64: W * P is a power of two
+  return b;
+}
+
+static int bands_args(const bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
+                      int64_t n_groups) {
+  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
+  if (!col_group || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  return BNF_OK;
+}
+
+int bnf_sample_depths(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
+                      int64_t n_groups, const double* y, int32_t* depth, int32_t* obs_depth) {
+  if (const int rc = bands_args(h, x, n_samples, n_cols, col_group, n_groups)) return rc;
+  if (!depth) return fail(BNF_ERR_INVALID, "depth is NULL");
+  if ((y == nullptr) != (obs_depth == nullptr)) return fail(BNF_ERR_INVALID, "y and obs_depth are given together or not at all");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const BandSlab b = band_slab(n_samples);
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_sample_depths, (int)(sizeof(uint64_t) * kSumMaxSamples), &attr_done);
+  hipLaunchKernelGGL(k_sample_depths, dim3(cdiv(n_cols, b.W)), dim3(b.threads), sizeof(uint64_t) * (size_t)b.W * (size_t)b.P,
+                     h->stream, x, (int32_t)n_samples, n_cols, (int32_t)b.P, (int32_t)b.W, col_group, (int32_t)n_groups, y,
+                     depth, obs_depth);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_depth_levels(bnf_handle* h, const int32_t* depth, int64_t n_samples, int64_t n_groups, const int32_t* need,
+                     int32_t n_cov, const int32_t* k_query, int32_t n_query, const int32_t* obs_depth, int32_t* level,
+                     double* achieved, double* joint, double* obs_pit) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (!depth || n_samples < 1 || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  if (n_samples > BNF_SUMMARY_MAX_SAMPLES)
+    return fail(BNF_ERR_INVALID, "%lld sample paths: the depths are counted in LDS, at most %d", (long long)n_samples,
+                BNF_SUMMARY_MAX_SAMPLES);
+  if (n_cov < 0 || n_cov > BNF_BAND_MAX_LEVELS || (n_cov > 0 && (!need || (!level && !achieved))))
+    return fail(BNF_ERR_INVALID, "n_cov = %d: 0..%d coverage levels, with need and level or achieved", n_cov,
+                BNF_BAND_MAX_LEVELS);
+  if (n_query < 0 || n_query > BNF_BAND_MAX_LEVELS || (n_query > 0 && (!k_query || !joint)))
+    return fail(BNF_ERR_INVALID, "n_query = %d: 0..%d band levels, with k_query and joint", n_query, BNF_BAND_MAX_LEVELS);
+  if (obs_pit && !obs_depth) return fail(BNF_ERR_INVALID, "obs_pit needs obs_depth");
+  if (n_cov < 1 && n_query < 1 && !obs_pit) return fail(BNF_ERR_INVALID, "no output asked for");
+  BandLevels q;
+  q.n_cov = n_cov;
+  q.n_query = n_query;
+  for (int32_t i = 0; i < kBandMaxLevels; ++i) { q.need[i] = 1; q.k_query[i] = 0; }
+  for (int32_t i = 0; i < n_cov; ++i) {
+    if (need[i] < 1 || need[i] > n_samples)
+      return fail(BNF_ERR_INVALID, "need = %d: 1..%lld, the number of sample paths", need[i], (long long)n_samples);
+    q.need[i] = need[i];
+  }
+  for (int32_t i = 0; i < n_query; ++i) q.k_query[i] = k_query[i];
+  HIPCHK(hipSetDevice(h->cfg.device));
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_depth_levels, (int)(sizeof(int32_t) * (kSumMaxSamples + 1)), &attr_done);
+  hipLaunchKernelGGL(k_depth_levels, dim3((unsigned)n_groups), dim3(kBandThreads), sizeof(int32_t) * (size_t)(n_samples + 1),
+                     h->stream, depth, (int32_t)n_samples, (int32_t)n_groups, q, obs_depth, level, achieved, joint, obs_pit);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_sample_envelope(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
+                        const int32_t* level, int32_t n_levels, int64_t n_groups, double* lower, double* upper) {
+  if (const int rc = bands_args(h, x, n_samples, n_cols, col_group, n_groups)) return rc;
+  if (!level || !lower || !upper) return fail(BNF_ERR_INVALID, "level, lower or upper is NULL");
+  if (n_levels < 1 || n_levels > BNF_BAND_MAX_LEVELS)
+    return fail(BNF_ERR_INVALID, "n_levels = %d: 1..%d", n_levels, BNF_BAND_MAX_LEVELS);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const BandSlab b = band_slab(n_samples);
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &k_sample_envelope, (int)(sizeof(uint64_t) * kSumMaxSamples), &attr_done);
+  hipLaunchKernelGGL(k_sample_envelope, dim3(cdiv(n_cols, b.W)), dim3(b.threads),
+                     sizeof(uint64_t) * (size_t)b.W * (size_t)b.P, h->stream, x, (int32_t)n_samples, n_cols, (int32_t)b.P,
+                     (int32_t)b.W, col_group, (int32_t)n_groups, level, n_levels, lower, upper);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

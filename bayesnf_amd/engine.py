@@ -861,6 +861,120 @@ class Engine:
     torch.cuda.synchronize(self.device)     # device copies made here are released on return
     return out
 
+  def _band_inputs(self, x, col_group, n_groups):
+    """x (S, C) f64, col_group (C,) int32 on the device, and the sizes checked -> (x, col_group, S, C, G)."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, C_ = x.shape
+    if S < 1 or C_ < 1:
+      raise ValueError(f'x must hold at least one path and one column; got {tuple(x.shape)}')
+    if S > _native.SUMMARY_MAX_SAMPLES:
+      raise ValueError(f'{S} sample paths: a column is sorted in LDS, at most {_native.SUMMARY_MAX_SAMPLES}')
+    G = int(n_groups)
+    if G < 1:
+      raise ValueError(f'n_groups={G}: need at least one group')
+    cg = (col_group if isinstance(col_group, torch.Tensor)
+          else torch.from_numpy(np.ascontiguousarray(col_group, dtype=np.int32))).to(self.device, dtype=torch.int32).contiguous()
+    if tuple(cg.shape) != (C_,):
+      raise ValueError(f'col_group must hold one group per column ({C_},); got {tuple(cg.shape)}')
+    return x, cg, S, C_, G
+
+  def sample_depths(self, x, col_group, n_groups, y=None, depth=None, obs_depth=None) -> dict:
+    """The depth of every joint path of x (S, C) f64 in every group of columns (include/bnf.h bnf_sample_depths):
+    col_group (C,) int32 the group of every column, an entry outside [0, n_groups) = the column takes no part -> dict of
+    int32 device tensors:
+      'depth' (S, G)      min over the group's columns of min(#{x_t <= x_s}, #{x_t >= x_s}) - 1; path s lies inside the band
+                          [x_(k), x_(S-1-k)] at every column of g exactly when depth[s][g] >= k.  -1 in a group with a NaN
+                          column, BNF_DEPTH_NONE (0x7fffffff) in a group without columns
+      'obs_depth' (G,)    with y (C,), the observed values (NaN: takes no part): the same for the observed curve, -1 =
+                          outside the envelope of all paths; BNF_DEPTH_NONE where no column has an observed value
+    depth / obs_depth: tensors an earlier call returned -- the call lowers them further, so chunks of columns, or several
+    curves of the same paths, accumulate into one joint depth; None: allocated here and filled with BNF_DEPTH_NONE.
+    More than BNF_SUMMARY_MAX_SAMPLES paths is a ValueError.  Integer atomicMin only: deterministic."""
+    x, cg, S, C_, G = self._band_inputs(x, col_group, n_groups)
+    y = None if y is None else self._as_f64(y, (C_,), 'y')
+
+    def held(t, shape, what):
+      if t is None:
+        return torch.full(shape, _native.DEPTH_NONE, dtype=torch.int32, device=self.device)
+      if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
+              and t.device == x.device):
+        raise ValueError(f'{what} must be the contiguous int32 device tensor {shape} an earlier call returned')
+      return t
+
+    out = {'depth': held(depth, (S, G), 'depth')}
+    if y is not None:
+      out['obs_depth'] = held(obs_depth, (G,), 'obs_depth')
+    elif obs_depth is not None:
+      raise ValueError('obs_depth accumulates the depth of the observed values: it needs y')
+    _native.check(self.lib.bnf_sample_depths(self.handle, _ptr(x), S, C_, _ptr(cg), G, _ptr(y), _ptr(out['depth']),
+                                             _ptr(out.get('obs_depth'))), 'bnf_sample_depths')
+    torch.cuda.synchronize(self.device)     # device copies of `x`, `col_group` and `y` made here are released on return
+    return out
+
+  def depth_levels(self, depth, need, k_query=(), obs_depth=None) -> dict:
+    """The band levels that hold `need` whole paths, from the (S, G) int32 depths `sample_depths` returns (include/bnf.h
+    bnf_depth_levels).  need: ints in [1, S] (`inference.band_need`); k_query: band levels to evaluate -> dict of device
+    tensors:
+      'level' (len(need), G) int32      the largest k with #{s : depth >= k} >= need: the need-th largest depth of the group
+      'achieved' (len(need), G) f64     #{s : depth >= level} / S >= need / S
+      'joint' (len(k_query), G) f64     with k_query: #{s : depth >= k_query} / S, the share of the paths band k holds whole
+      'obs_pit' (2, G) f64              with obs_depth (G,) int32: #{depth <= obs_depth} / S and #{depth < obs_depth} / S;
+                                        NaN where obs_depth is BNF_DEPTH_NONE
+    A group without columns (a depth outside [-1, S - 1]) has level -1 and NaN ratios; a group with a NaN column level -1
+    and achieved 1.  At most BNF_BAND_MAX_LEVELS entries in need and in k_query, a need outside [1, S] is the library's
+    error (ValueError).  Deterministic."""
+    if not (isinstance(depth, torch.Tensor) and depth.dim() == 2 and depth.dtype == torch.int32):
+      raise ValueError('depth must be the (n_samples, n_groups) int32 device tensor sample_depths returns')
+    depth = depth.to(self.device).contiguous()
+    S, G = depth.shape
+    if S < 1 or G < 1:
+      raise ValueError(f'depth must hold at least one path and one group; got {tuple(depth.shape)}')
+    need = [int(v) for v in need]
+    k_query = [int(v) for v in k_query]
+    if not need:
+      raise ValueError('need: at least one count of paths to hold')
+    if max(len(need), len(k_query)) > _native.BAND_MAX_LEVELS:
+      raise ValueError(f'{len(need)} coverage levels, {len(k_query)} queried bands: at most {_native.BAND_MAX_LEVELS} each')
+    if obs_depth is not None:
+      if not (isinstance(obs_depth, torch.Tensor) and obs_depth.dtype == torch.int32 and tuple(obs_depth.shape) == (G,)):
+        raise ValueError(f'obs_depth must be the ({G},) int32 device tensor sample_depths returns')
+      obs_depth = obs_depth.to(self.device).contiguous()
+    out = {'level': torch.empty((len(need), G), dtype=torch.int32, device=self.device),
+           'achieved': torch.empty((len(need), G), dtype=torch.float64, device=self.device)}
+    if k_query:
+      out['joint'] = torch.empty((len(k_query), G), dtype=torch.float64, device=self.device)
+    if obs_depth is not None:
+      out['obs_pit'] = torch.empty((2, G), dtype=torch.float64, device=self.device)
+    clamp = lambda v: max(-0x80000000, min(0x7fffffff, v))
+    na = (C.c_int32 * len(need))(*[clamp(v) for v in need])
+    ka = (C.c_int32 * max(1, len(k_query)))(*[clamp(v) for v in k_query])
+    _native.check(self.lib.bnf_depth_levels(
+        self.handle, _ptr(depth), S, G, na, len(need), ka, len(k_query), _ptr(obs_depth), _ptr(out['level']),
+        _ptr(out['achieved']), _ptr(out.get('joint')), _ptr(out.get('obs_pit'))), 'bnf_depth_levels')
+    torch.cuda.synchronize(self.device)     # device copies made here are released on return
+    return out
+
+  def sample_envelope(self, x, col_group, level) -> dict:
+    """The bands [x_(k), x_(S-1-k)] of the columns of x (S, C) f64 at the levels k = level[j][group of the column]
+    (include/bnf.h bnf_sample_envelope): col_group (C,) int32 as for `sample_depths`, level (n_levels, G) int32 as
+    `depth_levels` returns it -> {'lower', 'upper'}: (n_levels, C) f64 device tensors, values picked from x; NaN where the
+    level is outside [0, S - 1], the column takes no part or holds a NaN sample.  Deterministic."""
+    if not (isinstance(level, torch.Tensor) and level.dim() == 2 and level.dtype == torch.int32):
+      raise ValueError('level must be the (n_levels, n_groups) int32 device tensor depth_levels returns')
+    level = level.to(self.device).contiguous()
+    L, G = level.shape
+    x, cg, S, C_, G = self._band_inputs(x, col_group, G)
+    if not 1 <= L <= _native.BAND_MAX_LEVELS:
+      raise ValueError(f'{L} levels: 1..{_native.BAND_MAX_LEVELS}')
+    out = {'lower': torch.empty((L, C_), dtype=torch.float64, device=self.device),
+           'upper': torch.empty((L, C_), dtype=torch.float64, device=self.device)}
+    _native.check(self.lib.bnf_sample_envelope(self.handle, _ptr(x), S, C_, _ptr(cg), _ptr(level), L, G, _ptr(out['lower']),
+                                               _ptr(out['upper'])), 'bnf_sample_envelope')
+    torch.cuda.synchronize(self.device)     # device copies of `x` and `col_group` made here are released on return
+    return out
+
   # -- introspection (tests, bench) -------------------------------------------
   def debug_loss_and_grad(self, epoch=0, step=0):
     k = 2 if self.mode == 'vi' else 1

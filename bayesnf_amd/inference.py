@@ -16,6 +16,7 @@ per torchrun rank -- is `distributed.local_shards()`.
 from __future__ import annotations
 
 import contextlib
+import math
 import numbers
 import os
 import warnings
@@ -1064,6 +1065,133 @@ def window_summaries(features, observation_model, params, model_args, num_sample
     if threshold is not None:
       out['exceed_probability'] = wi['exceed_count'].cpu().numpy().astype(np.float64) / num_samples
       out['any'] = (wi['count'] > 0).sum(dim=0).cpu().numpy().astype(np.float64) / num_samples
+    return out
+
+
+def band_need(coverage, num_samples):
+  """The number of whole sample paths a simultaneous band of the given coverage must hold: ceil(coverage * num_samples),
+  formed as ceil(coverage * num_samples - 1e-9) because a product such as 0.07 * 100 is 7.000000000000001 in float64, clamped to
+  [1, num_samples].  coverage in (0, 1], ValueError otherwise."""
+  try:
+    c = float(coverage)
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'coverage must be a number in (0, 1]; got {coverage!r}') from e
+  if not 0.0 < c <= 1.0:
+    raise ValueError(f'coverage must lie in (0, 1]; got {coverage!r}')
+  num_samples = int(num_samples)
+  if num_samples < 1:
+    raise ValueError(f'num_samples={num_samples}: need at least one sample path')
+  return max(1, min(num_samples, int(math.ceil(c * num_samples - 1e-9))))
+
+
+def _coverage_levels(coverage):
+  try:
+    levels = [float(v) for v in coverage]
+  except (TypeError, ValueError) as e:
+    raise ValueError(f'coverage must be a sequence of numbers in (0, 1]; got {coverage!r}') from e
+  if not levels or len(levels) > _native.BAND_MAX_LEVELS:
+    raise ValueError(f'coverage: 1..{_native.BAND_MAX_LEVELS} levels; got {len(levels)}')
+  if any(not 0.0 < v <= 1.0 for v in levels):
+    raise ValueError(f'coverage must lie in (0, 1]; got {levels}')
+  return levels
+
+
+BAND_OF = ('rows', 'cumulative')
+
+
+def band_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
+                   coverage=(0.9,), of='rows', observed=None, compute_dtype=None, weights=None):
+  """SIMULTANEOUS bands of the joint sample paths, per group of rows, on the GPU (include/bnf.h bnf_sample_depths,
+  bnf_depth_levels, bnf_sample_envelope): bands that hold a whole path over the rows of a group with probability
+  `coverage`, where a quantile band holds each row alone -- the rank envelope: band k at a row is [x_(k), x_(S-1-k)] of the
+  row's S sorted samples, and the level of a group is the largest k whose band still holds ceil(coverage S) of the paths
+  (`band_need`) at EVERY row of the group.  groups = (seg_offsets, seg_rows);
+    of='rows'         the curve of a group is the draws at its rows (`csr_from_codes`; a row in no group takes no part)
+    of='cumulative'   the curve is the running total along the group's rows in TIME order (`csr_ordered`), as
+                      `cumulative_summaries` forms it
+  observed (n_rows,), per TABLE ROW: the observed value (of='cumulative': the observed running total) at the row, NaN
+  where it takes no part.  -> dict of numpy arrays, n_cov = len(coverage):
+    'level' (n_cov, G) int32                 the band level k* of the group; -1 for a group without rows and one with a NaN draw
+    'coverage' (n_cov, G) float64            the share of the paths band k* holds whole: >= ceil(coverage S) / S
+    'pointwise_joint_coverage' (n_cov, G)    the share of the paths that the POINTWISE band holds whole: band
+                                             floor((S - need) / 2), which holds need samples at each row
+    'lower', 'upper' (n_cov, n_rows) float64             the simultaneous band, values picked from the samples
+    'pointwise_lower', 'pointwise_upper' (n_cov, n_rows) the pointwise band, for comparison
+  per-row results are NaN at a row that takes no part and at one with a NaN draw, the simultaneous band also at every other
+  row of that draw's group (its level is -1); with `observed`:
+    'observed_depth' (G,) float64   the largest band level that still holds the observed curve at every scored row, -1 = it
+                                    leaves the envelope of all paths; NaN for a group without an observed value
+    'inside' (n_cov, G) float64     1.0 where the simultaneous band holds the observed curve, 0.0 where not, NaN as above
+    'depth_pit' (2, G) float64      #{paths of depth <= the observed} / S and #{... <} / S: uniform between the two when the
+                                    observed curve is exchangeable with the paths; small = more extreme than nearly all
+  The matrix of curves is held whole: num_samples <= 16,384 and num_samples * n_rows <= 2^28 cells, ValueError beyond,
+  like every check before any GPU work.  weights: member weights of the sample paths as in `sample_predictive`."""
+  num_samples = _num_samples(num_samples, 'bands')
+  levels = _coverage_levels(coverage)
+  if of not in BAND_OF:
+    raise ValueError(f"of={of!r}: 'rows' (the draws at the rows) or 'cumulative' (their running totals)")
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  features = np.asarray(features, dtype=np.float64)
+  n_rows = features.shape[0]
+  if n_groups < 1:
+    raise ValueError('groups: need at least one group')
+  if of == 'cumulative' and len(seg_rows) != n_rows:
+    raise ValueError(f"of='cumulative': seg_rows must hold one entry per row ({n_rows}); got {len(seg_rows)}")
+  _check_cells(num_samples, n_rows, 'sample paths are')
+  if observed is not None:
+    observed = np.ascontiguousarray(observed, dtype=np.float64)
+    if observed.shape != (n_rows,):
+      raise ValueError(f'observed must hold one value per row ({n_rows},); got {observed.shape}')
+  need = [band_need(v, num_samples) for v in levels]
+  k_pw = [(num_samples - n) // 2 for n in need]
+  pos_rows = np.asarray(seg_rows, dtype=np.int64)
+  named = (pos_rows >= 0) & (pos_rows < n_rows)
+  pos_group = np.repeat(np.arange(n_groups, dtype=np.int32), np.diff(np.asarray(seg_offsets, dtype=np.int64)))
+  if pos_group.shape != pos_rows.shape:
+    raise ValueError(f'groups: seg_offsets covers {pos_group.size} positions, seg_rows holds {pos_rows.size}')
+  if of == 'rows':                              # column = table row
+    col_group = np.full(n_rows, -1, dtype=np.int32)
+    col_group[pos_rows[named]] = pos_group[named]
+    y_col = observed
+  else:                                         # column = position
+    col_group = np.where(named, pos_group, np.int32(-1)).astype(np.int32)
+    y_col = None
+    if observed is not None:
+      y_col = np.full(pos_rows.shape, np.nan)
+      y_col[named] = observed[pos_rows[named]]
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    if of == 'rows':
+      x = torch.empty((num_samples, n_rows), dtype=torch.float64, device=eng.device)
+      chunk = max(1, _SAMPLE_CHUNK_CELLS // num_samples)
+      for r0 in range(0, n_rows, chunk):
+        r1 = min(n_rows, r0 + chunk)
+        x[:, r0:r1] = eng.predictive_samples(loc[:, r0:r1], aux, num_samples, seed64, row0=r0, **kw)
+    else:
+      x = eng.predictive_group_cumulative(loc, aux, seg_offsets, seg_rows, num_samples, seed64, running=True, **kw)['running']
+    cg = torch.from_numpy(col_group).to(eng.device)
+    y = None if y_col is None else torch.from_numpy(y_col).to(eng.device)
+    dep = eng.sample_depths(x, cg, n_groups, y)
+    lev = eng.depth_levels(dep['depth'], need, k_pw, dep.get('obs_depth'))
+    out = {'level': lev['level'].cpu().numpy(), 'coverage': lev['achieved'].cpu().numpy()}
+    out['pointwise_joint_coverage'] = lev['joint'].cpu().numpy()          # row i: band k_pw[i], the one of coverage[i]
+    pw_level = torch.from_numpy(np.repeat(np.asarray(k_pw, dtype=np.int32)[:, None], n_groups, axis=1)).to(eng.device)
+    for prefix, lv in (('', lev['level']), ('pointwise_', pw_level)):
+      env = eng.sample_envelope(x, cg, lv)
+      for k in ('lower', 'upper'):
+        v = env[k].cpu().numpy()
+        if of == 'cumulative':                  # column = position: back to table rows through seg_rows
+          by_row = np.full((v.shape[0], n_rows), np.nan)
+          by_row[:, pos_rows[named]] = v[:, named]
+          v = by_row
+        out[prefix + k] = v
+    if y is not None:
+      od = dep['obs_depth'].cpu().numpy()
+      seen = od != _native.DEPTH_NONE
+      out['observed_depth'] = np.where(seen, od.astype(np.float64), np.nan)
+      out['inside'] = np.where(seen[None, :], (od[None, :] >= out['level']).astype(np.float64), np.nan)
+      out['depth_pit'] = lev['obs_pit'].cpu().numpy()
     return out
 
 

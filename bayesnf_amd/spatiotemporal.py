@@ -1238,6 +1238,89 @@ class BayesianNeuralFieldEstimator:
                  mean_count_crps=mean(out['count_crps']))
     return res
 
+  def _band_summaries(self, what, table, group_by, coverage, of, order_by, num_samples, seed, weights, target=False):
+    if self.params_ is None:
+      raise ValueError(f'{what} before fit')
+    if of not in inference.BAND_OF:
+      raise ValueError(f"{what}: of={of!r}: 'rows' (the draws at the rows) or 'cumulative' (their running totals)")
+    if of == 'rows' and order_by is not None:
+      raise ValueError(f"{what}: order_by orders a running total: it needs of='cumulative'")
+    if of == 'cumulative' and group_by is None:
+      raise ValueError(f"{what}: of='cumulative' needs group_by: a running total runs along the rows of a group")
+    f = self._paths(what, table, group_by, num_samples, seed, weights, noun='bands', target=target,
+                    ordered=of == 'cumulative', order_by=order_by)
+    try:
+      levels = inference._coverage_levels(coverage)
+    except ValueError as e:
+      raise ValueError(f'{what}: {e}') from e
+    if len(table) == 0:
+      raise ValueError(f'{what}: the table has no rows')
+    if int(num_samples) * len(table) > inference._TOTALS_MAX_CELLS:
+      raise ValueError(f'{what}: {num_samples} sample paths x {len(table)} rows: the sample paths are held whole on the '
+                       f'device, at most {inference._TOTALS_MAX_CELLS} cells')
+    keys, particular = f.keys, {}
+    seg_offsets, seg_rows = f.seg_offsets, f.seg_rows
+    if keys is None:                            # of='rows' without group_by: one group of all rows
+      keys = pd.RangeIndex(1)
+      seg_offsets = np.asarray([0, len(table)], dtype=np.int32)
+      seg_rows = np.arange(len(table), dtype=np.int32)
+      particular['groups'] = (seg_offsets, seg_rows)
+    observed = None
+    if f.y is not None:
+      observed = f.y if of == 'rows' else group_target_cumulative(f.y, seg_offsets, seg_rows)['running']
+      particular['observed'] = observed
+    out = f.run(inference.band_summaries, coverage=tuple(levels), of=of, **particular)
+    res = {'keys': keys}
+    res.update({k: out[k] for k in ('level', 'coverage', 'pointwise_joint_coverage', 'lower', 'upper', 'pointwise_lower',
+                                    'pointwise_upper')})
+    return res, out, observed
+
+  def predict_bands(self, table, group_by, coverage=(0.9,), of='rows', order_by=None, num_samples=1000, seed=0,
+                    weights=None):
+    """SIMULTANEOUS bands of the sample paths of `predict_samples(table, num_samples, seed)`: for every group a band that
+    holds a WHOLE path over the group's rows with probability `coverage`, formed on the GPU.  The quantiles of `predict`,
+    `predict_cumulative` and `predict_windows` are pointwise: each holds, say, 90 % of the paths at one row, and far fewer
+    paths stay inside at every row (`pointwise_joint_coverage` says how many); read a band of this method as "the curve
+    stays in here".  The construction is the rank envelope: band k at a row runs from the k-th smallest to the k-th largest
+    of the row's samples, and a group takes the largest k whose band still holds ceil(coverage * num_samples) paths whole.
+      of='rows'         the curve is the value at every row of the group; group_by=None: one group of all rows
+      of='cumulative'   the curve is the running total along the group's rows, ordered as in `predict_cumulative`
+                        (`order_by=None`: by the time column); needs group_by
+    -> dict, n_cov = len(coverage):
+      'keys'                                     the groups, as in `predict_samples` (RangeIndex(1) for group_by=None)
+      'level' (n_cov, G) int                     the band level k of the group, -1 where a draw of the group is NaN
+      'coverage' (n_cov, G)                      the share of the paths the band holds whole, >= the coverage asked for
+      'pointwise_joint_coverage' (n_cov, G)      the share of the paths that the pointwise band of the same coverage
+                                                 (the one holding ceil(coverage * num_samples) samples at each row) holds whole
+      'lower', 'upper' (n_cov, len(table))       the simultaneous band at every row (of='cumulative': of the running total)
+      'pointwise_lower', 'pointwise_upper' (n_cov, len(table))   the pointwise band, for comparison
+    1 <= len(coverage) <= 64, every level in (0, 1]; num_samples <= 16,384 and num_samples * len(table) <= 2^28.
+    weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    return self._band_summaries('predict_bands', table, group_by, coverage, of, order_by, num_samples, seed, weights)[0]
+
+  def score_bands(self, table, group_by, coverage=(0.9,), of='rows', order_by=None, num_samples=1000, seed=0, weights=None):
+    """The bands of `predict_bands` held against the curve observed in `table[target_col]` (of='cumulative': its running
+    total per group, `group_target_cumulative`), on the GPU: a JOINT calibration check, which neither the energy nor the
+    variogram score gives.  A NaN target takes no part (of='cumulative': nor does any later row of its group).  -> the
+    dict of `predict_bands` plus
+      'observed' (len(table),)      the observed curve, NaN where it takes no part
+      'observed_depth' (G,)         the largest band level that holds the observed curve at every scored row of the group;
+                                    -1: it leaves the envelope of all paths; NaN: no row of the group is scored
+      'inside' (n_cov, G)           1.0 / 0.0: the band of that coverage holds the observed curve or not; NaN as above
+      'depth_pit' (2, G)            the share of the paths whose depth is <= and < the observed curve's: a value drawn
+                                    uniformly between the two is uniform for a calibrated forecast; near 0 = the observed
+                                    curve is more extreme than nearly every path
+      'n'                           number of groups scored       'share_inside' (n_cov,)   mean of 'inside' over them
+    The target checks are those of `score_totals`."""
+    res, out, observed = self._band_summaries('score_bands', table, group_by, coverage, of, order_by, num_samples, seed,
+                                              weights, target=True)
+    scored = ~np.isnan(out['observed_depth'])
+    share = (np.mean(out['inside'][:, scored], axis=1, dtype=np.float64) if scored.any()
+             else np.full(out['inside'].shape[0], np.nan))
+    res.update(observed=observed, observed_depth=out['observed_depth'], inside=out['inside'], depth_pit=out['depth_pit'],
+               n=int(scored.sum()), share_inside=share)
+    return res
+
   def _dependence_summaries(self, what, table, group_by, num_samples, seed, weights, target=False, p=0.5,
                             pair_weights=None, matrices=True):
     f = self._paths(what, table, group_by, num_samples, seed, weights, target=target)

@@ -742,6 +742,60 @@ int bnf_sample_ranks(bnf_handle* h, const double* x, int64_t n_samples, int64_t 
 int bnf_rank_probabilities(bnf_handle* h, const int32_t* above, const int32_t* ties, int64_t n_samples, int64_t n_cols,
                            int32_t top_k, double* out);
 
+/* SIMULTANEOUS BANDS of the joint sample paths: bands that hold a whole path with a given probability, where the quantiles
+ * of bnf_sample_summaries hold each column alone -- the rank envelope of Myllymaki et al. 2017 ("Global envelope tests").
+ * x as for bnf_sample_summaries, S = n_samples, C = n_cols (a column is a table row, or a position of a running-total
+ * curve); col_group DEVICE (C,) int32 the group of every column, an entry outside [0, G) = the column takes no part;
+ * G = n_groups.  Comparisons use the total order of bnf_sample_ranks: -0.0 == +0.0, infinities of one sign tie.
+ *   depth of path s at column c   d_sc = min(#{t : x_tc <= x_sc}, #{t : x_tc >= x_sc}) - 1, in [0, S - 1] (s counts itself);
+ *                                 in a column that holds a NaN sample every path has depth -1
+ *   depth of path s in group g    D_sg = min of d_sc over the columns of g
+ *   band k at a column            [x_(k), x_(S-1-k)] of the column sorted ascending, 0-indexed; path s lies inside band k at
+ *                                 every column of g exactly when D_sg >= k
+ * Everything is an integer, a value picked from x, or ONE f64 division of a count by (double)S.
+ * bnf_sample_depths: lowers depth DEVICE (S, G) int32 to min(depth, D) with integer atomicMin only; the CALLER fills it
+ *   with BNF_DEPTH_NONE first, so several calls -- over chunks of columns, or over several curves of the same paths --
+ *   accumulate into one joint depth, in any order.  A group no column of the call belongs to is not touched.
+ *   y DEVICE (C,) f64 observed values, or NULL: obs_depth DEVICE (G,) int32, pre-filled the same way, is lowered to
+ *     OD_g = min over the columns of g whose y_c is not NaN of od_c = min(#{t : x_tc <= y_c}, #{t : x_tc >= y_c}) - 1,
+ *     in [-1, S - 1]: -1 = outside the envelope of all paths at some column (and in a column with a NaN sample); y lies
+ *     inside band k of g exactly when OD_g >= k.  y and obs_depth are NULL together (BNF_ERR_INVALID otherwise).
+ *   One workgroup sorts a slab of up to 8 adjacent columns in LDS (the layout of bnf_sample_summaries, 8 bytes a key,
+ *   padded to a power of two with a key above every real one) and every (path, column) finds its tie block by two binary
+ *   searches over the real cells only: C S log^2 S / 2 compare-exchanges, 2 C S log S probes.
+ * bnf_depth_levels: from depth (and obs_depth, or NULL) as bnf_sample_depths left them, with ge_g(k) = #{s : D_sg >= k}:
+ *   need HOST n_cov int32 in [1, S]: for a coverage c, ceil(c S) (the caller rounds); k_query HOST n_query int32, any value;
+ *     both travel as kernel arguments: n_cov, n_query <= BNF_BAND_MAX_LEVELS
+ *   level DEVICE (n_cov, G) int32: k* = the largest k with ge_g(k) >= need_i -- the need_i-th largest of D[:, g], in [-1, S - 1]
+ *   achieved DEVICE (n_cov, G) f64: ge_g(k*) / S >= need_i / S, the share of the paths that band k* holds whole
+ *   joint DEVICE (n_query, G) f64: ge_g(k_query_i) / S -- e.g. with k = floor((S - need) / 2), the pointwise band that holds
+ *     need samples at each column, the share of the paths that band holds WHOLE
+ *   obs_pit DEVICE (2, G) f64: [0] = #{s : D_sg <= OD_g} / S, [1] = #{s : D_sg < OD_g} / S: the depth PIT of the observed
+ *     curve (a value drawn uniformly between the two is uniform when y is exchangeable with the paths; small = the observed
+ *     curve is more extreme than nearly every path).  NaN where OD_g is outside [-1, S - 1] (no observed column).  Needs
+ *     obs_depth
+ *   Each output is skipped when NULL.  A group with a depth outside [-1, S - 1] is EMPTY (BNF_DEPTH_NONE: no column took
+ *   part; or the input is not ours): level -1 and NaN ratios; such a value never indexes anything.  A group poisoned by a
+ *   NaN column (every depth -1) has level -1 and achieved 1.  One workgroup per group: a histogram of D + 1 over S + 1 bins
+ *   in LDS (integer atomics), a suffix scan, then every output is a lookup: S + G reads of depth, no sort.
+ * bnf_sample_envelope: the bands themselves.  level DEVICE (n_levels, G) int32 as bnf_depth_levels writes it (or any k);
+ *   lower, upper DEVICE (n_levels, C) f64: lower[j][c] = x_(k), upper[j][c] = x_(S-1-k) with k = level[j][group of c]; NaN
+ *   for k outside [0, S - 1], for a column that takes no part and for one that holds a NaN sample.  A picked -0.0 comes
+ *   back as +0.0.  The same slab sort, then picks.  1 <= n_levels <= BNF_BAND_MAX_LEVELS.
+ * All three: BNF_ERR_INVALID with nothing launched for a NULL required pointer, n_samples, n_cols or n_groups < 1,
+ * n_samples > BNF_SUMMARY_MAX_SAMPLES, a need outside [1, n_samples] and more levels than BNF_BAND_MAX_LEVELS.  No
+ * floating-point atomics, two calls give the same bits; they run on the handle's stream, do not touch the training state,
+ * work on forward-only handles; the observation model of the handle plays no part. */
+#define BNF_DEPTH_NONE 0x7fffffff        /* the pre-fill of depth and obs_depth: no column has been seen */
+#define BNF_BAND_MAX_LEVELS 64           /* coverage levels / queried bands per call */
+int bnf_sample_depths(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
+                      int64_t n_groups, const double* y, int32_t* depth, int32_t* obs_depth);
+int bnf_depth_levels(bnf_handle* h, const int32_t* depth, int64_t n_samples, int64_t n_groups, const int32_t* need,
+                     int32_t n_cov, const int32_t* k_query, int32_t n_query, const int32_t* obs_depth, int32_t* level,
+                     double* achieved, double* joint, double* obs_pit);
+int bnf_sample_envelope(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
+                        const int32_t* level, int32_t n_levels, int64_t n_groups, double* lower, double* upper);
+
 /* ---- introspection used by tests and bench.py ------------------------------ */
 /* One forward+backward of every local member on batch `step` of `epoch` WITHOUT
  * the optimiser update: grads DEVICE (members*S, P) f32 receives d(step loss)/d
