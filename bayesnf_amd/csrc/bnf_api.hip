@@ -122,6 +122,7 @@ struct bnf_handle {
   int32_t* fbmeta = nullptr;
   std::vector<int32_t> fbmeta_h;
   int fb_in_group = -1;
+  int n_fourier = 0;          // Fourier feature columns of the model (StepPlan::featbwd_in_wgrad takes at most kSkFbCols)
   int64_t N = 0, B = 0, Bp = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;            // weight-gradient contractions overlap the dgrad chain
@@ -473,6 +474,23 @@ static void launch_gemm_tn_skinny(bnf_handle* h, int kid, GemmArgs g, const EpiA
   LaunchScope ls(h, kid, st, true);
   hipLaunchKernelGGL(gemm_tn_skinny, dim3(blocks), dim3(512), kSkLds, st, g, ep);
 }
+// the same stream with the fused featurisation backward in it (StepPlan::featbwd_in_wgrad: bf16, Fp = 64, the column
+// table exists, at most kSkFbCols Fourier columns); the panel kernel of this step ended behind its dZ0 epilogue
+static void launch_gemm_tn_skinny_featbwd(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep, hipStream_t st) {
+  g.tiles_m = 1;
+  g.tiles_n = g.N / 512;
+  if (g.splitk < 1) g.splitk = 1;
+  FeatBwdArgs fw{};
+  fw.Wb0 = (const bf16_t*)h->Wb[0]; fw.wb_batch = h->pack_batch[0];
+  fw.scal = h->scal; fw.fbmeta = h->fbmeta;
+  fw.F = h->F; fw.off_lsa = h->nd.off_lsa; fw.n_groups = h->nd.n_groups; fw.n_inputs = h->nd.D;
+  fw.scal_stride = kScalStride; fw.scal_gfac = kScalGfac; fw.scal_sp_in = kScalGroup + h->fb_in_group;
+  static std::atomic<uint64_t> attr_done{0};
+  allow_lds(h, &gemm_tn_skinny_featbwd, kSkLdsFb, &attr_done);
+  const unsigned blocks = (unsigned)((int64_t)g.members * g.tiles_n * g.splitk);
+  LaunchScope ls(h, kid, st, true);
+  hipLaunchKernelGGL(gemm_tn_skinny_featbwd, dim3(blocks), dim3(512), kSkLdsFb, st, g, ep, fw);
+}
 // `kind`: what wgrad_plan chose (WG_*); g.splitk is the plan's too
 template <typename T, int TAG>
 static void launch_gemm_tn(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep, hipStream_t st, int kind) {
@@ -626,13 +644,15 @@ struct LossSink {
   const StepState* st = nullptr;               // graph replay: per-step state in device memory
 };
 
-static_assert(kPlanBM == kBM && kPlanBN == kBN && kPlanSkRows == kSkRows, "bnf_plan.h counts tiles of the kernels' sizes");
+static_assert(kPlanBM == kBM && kPlanBN == kBN && kPlanSkRows == kSkRows && kPlanFbCols == kSkFbCols,
+              "bnf_plan.h counts tiles of the kernels' sizes");
 
 static PlanShape plan_shape(const bnf_handle* h) {
   PlanShape ps{};
   ps.bf16 = h->bf16; ps.L = h->L; ps.W = h->W; ps.F = h->F; ps.Fp = h->Fp; ps.Bp = h->Bp;
   ps.num_cus = h->num_cus; ps.panel = h->panel; ps.pad = h->pad;
   for (int l = 0; l < h->L; ++l) ps.off_kernel[l] = h->nd.off_kernel[l];
+  ps.fp8 = h->q8; ps.featbwd_fused = !h->fbmeta_h.empty(); ps.n_fourier = h->n_fourier;
   return ps;
 }
 
@@ -661,6 +681,12 @@ static void run_wgrad_layer(bnf_handle* h, int nmem, int l, hipStream_t st) {
       ep.qscale = h->qscale;
       if (l == 0) launch_gemm_tn8<0>(h, KID_WGRAD0, g, ep, st, plan.kind);
       else launch_gemm_tn8<1>(h, KID_WGRAD, g, ep, st, plan.kind);
+      return;
+    }
+  }
+  if constexpr (sizeof(T) == 2) {
+    if (l == 0 && h->plan.featbwd_in_wgrad) {
+      launch_gemm_tn_skinny_featbwd(h, KID_WGRAD0, g, ep, st);
       return;
     }
   }
@@ -857,12 +883,12 @@ static void run_pack_fragments(bnf_handle* h, const float* theta, int nmem) {
 // row-panel pipeline (bf16, depth 2): pack fragments -> featurise -> k_panel_fwd_bwd ->
 // featurise backward -> gemm_tn weight gradients
 // ---------------------------------------------------------------------------
-template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP, bool F0, bool C8 = false>
+template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP, bool F0, bool C8 = false, bool FBW = false>
 static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
   constexpr int kLds = panel_lds_bytes(WN, RT, H0L, CH, FP);
   static_assert(kLds <= 160 * 1024, "LDS per workgroup");
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8>, kLds, &attr_done);
+  allow_lds(h, &k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW>, kLds, &attr_done);
   PanelArgs pa2 = pa;
   pa2.ablate = h->sw.ablate;
   const unsigned blocks = (unsigned)(pa.members * pa.panels);
@@ -873,12 +899,21 @@ static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
   }
   {
     LaunchScope ls(h, KID_PANEL);
-    hipLaunchKernelGGL((k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8>), dim3(blocks), dim3(512), kLds, h->stream, pa2);
+    hipLaunchKernelGGL((k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW>), dim3(blocks), dim3(512), kLds, h->stream, pa2);
   }
   phase_prof_end(h, KID_PANEL, blocks, 512);
 }
 template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP>
 static void launch_panel_d(bnf_handle* h, const PanelArgs& pa) {
+  if constexpr (H0L && WN == 8 && FP == 64) {
+    // the plan moved the featurisation backward into the layer-0 weight gradient (bf16, W = 512 / 1024, Fp = 64): the
+    // forms that end behind the dZ0 epilogue
+    if (h->plan.featbwd_in_wgrad) {
+      if (h->fold0) launch_panel_f<WN, RT, H0L, DEEP, CH, FP, true, false, true>(h, pa);
+      else launch_panel_f<WN, RT, H0L, DEEP, CH, FP, false, false, true>(h, pa);
+      return;
+    }
+  }
   if constexpr (H0L) {
     if (h->fold0) {
       if (pa.c8) {      // fp8 W x W contractions: the folded forms (bnf_create decides h->c8)
@@ -1542,7 +1577,8 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
     if (in_group >= 0) {
       std::vector<int32_t>& m = h->fbmeta_h;
       const int Fp = h->Fp;                 // 64 or 128 (h0l); the group offsets follow the column entries
-      m.assign(Fp * 4 + BNF_MAX_GROUPS, 0);
+      // ... and the slots of the Fourier columns (FeatBwdArgs::fbmeta: the layer-0 weight gradient's extra operand rows)
+      m.assign(Fp * 4 + BNF_MAX_GROUPS + kSkFbCols, 0);
       auto put = [&](int col, int kind, int g, int d1, int d2, int partner, int ucol, float coef) {
         m[4 * col] = kind | (g << 8) | (d1 << 16) | (d2 << 24);
         m[4 * col + 1] = partner | (ucol << 8);
@@ -1575,6 +1611,13 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
         }
       }
       h->fb_in_group = in_group;
+      h->n_fourier = 0;
+      for (int c = 0; c < Fp; ++c) {
+        if ((m[4 * c] & 0xff) != kFbFourier) continue;
+        if (h->n_fourier < kSkFbCols && Fp == 64)
+          m[4 * Fp + BNF_MAX_GROUPS + h->n_fourier] = c | ((m[4 * c + 1] & 0xffff) << 8) | (1 << 24);
+        ++h->n_fourier;
+      }
     }
   }
   h->plan = make_step_plan(plan_shape(h), h->sw, h->Ev, cfg->mode == BNF_MODE_VI);   // (num_cus, panel and Bp are final)
@@ -3080,6 +3123,9 @@ void bnf_comm_destroy(bnf_comm* c) {
 double bnf_kernel_flops(const bnf_handle* h, const char* name) {
   if (!h || !name) return 0.0;
   const double Ev = h->Ev, B = (double)h->B, W = h->Wt, F = h->F;
+  // featbwd_in_wgrad: the panel kernel no longer contracts dH0 (below); the layer-0 weight gradient contracts the
+  // 2 x n_fourier rows of G (bf16 hi + lo) beside the F feature rows
+  if (!strcmp(name, "gemm_wgrad_l0") && h->plan.featbwd_in_wgrad) return 2.0 * Ev * B * (F + 2.0 * h->n_fourier) * W;
   if (!strcmp(name, "gemm_fwd_l0") || !strcmp(name, "gemm_dgrad0") || !strcmp(name, "gemm_wgrad_l0"))
     return 2.0 * Ev * B * F * W;
   if (!strcmp(name, "gemm_wgrad") && h->plan.merged)   // one launch for the layers 1 .. L-1
@@ -3089,7 +3135,7 @@ double bnf_kernel_flops(const bnf_handle* h, const char* name) {
   if (!strcmp(name, "gemm_fwd_last"))   // last hidden layer + output-layer dot
     return 2.0 * Ev * B * (h->L > 1 ? W : F) * W + 2.0 * Ev * B * W;
   if (!strcmp(name, "panel_fwd_bwd"))  // forward + backward-data contractions of every layer + output layer
-    return 4.0 * Ev * B * (F * W + (h->L - 1) * W * W) + 2.0 * Ev * B * W;
+    return 4.0 * Ev * B * (F * W + (h->L - 1) * W * W) + 2.0 * Ev * B * W - (h->plan.featbwd_in_wgrad ? 2.0 * Ev * B * F * W : 0.0);
   return 0.0;
 }
 

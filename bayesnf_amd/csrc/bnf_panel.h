@@ -4,7 +4,8 @@
 //   <8, 2, H0L, ., 2, 64>   W = 1024: 64-row panels, two 64-column slabs per wave      (C4)
 //   <4, 2, true, ., 1, FP>  W = 256: 128-row panels of two 64-row blocks, FP = 64 | 128 (C1, C5)
 //   <4, 4, false, ., 1, 64> W = 256 without the LDS feature panel: 256-row panels
-// (+ a last flag F0 on the H0L forms: layer 0 folded into its contraction, see k_panel_fwd_bwd)
+// (+ flags on the H0L forms, see k_panel_fwd_bwd -- F0: layer 0 folded into its contraction; C8: fp8 W x W contractions;
+// FBW, always LAST: the kernel ends behind the dZ0 epilogue, the featurisation backward is the layer-0 weight gradient's)
 //
 // A workgroup (8 waves, one per CU: 256 registers per lane) owns a panel of BM batch rows of one
 // ensemble member and carries it through the network and back (reference models.py:212-273,
@@ -19,7 +20,8 @@
 // What leaves the chip is exactly what the weight-gradient contractions (gemm_tn) and the feature
 // backward kernel read afterwards: H1, dZ1, dZ0 (bf16, row-major) and dH0^T -- the latter only for
 // the variants that still run k_feat_bwd: the H0L forms finish the featurisation backward
-// themselves from the dH0 tiles in registers and the feature panel in LDS (phase 9).  It replaces
+// themselves from the dH0 tiles in registers and the feature panel in LDS (phase 9) -- or, FBW, leave it to the layer-0
+// weight-gradient kernel, which forms it from its own accumulators (gemm_tn_skinny_featbwd, bnf_gemm.h).  It replaces
 // gemm_fwd_l0 + gemm_fwd_last + gemm_dgrad + gemm_dgrad0 of the layer pipeline (and their HBM
 // round trips of H1 / dZ1 / dZ0 as contraction operands: 2.0 GB of the 8.0 GB per C2 step).
 //
@@ -97,7 +99,8 @@ struct PanelArgs {
   // k_feat_bwd) is finished here from the dH0 tiles in registers and the feature panel in LDS;
   // dH0^T is then not written at all.  fbmeta: per feature column 4 words {kind | group << 8 |
   // d1 << 16 | d2 << 24, partner | ucol << 8, coefficient (float bits), 0} followed by the
-  // theta offsets of the BNF_MAX_GROUPS group scales (build_featbwd_meta in bnf_api.hip).
+  // theta offsets of the BNF_MAX_GROUPS group scales and the kSkFbCols slots of the Fourier columns (FeatBwdArgs of
+  // bnf_gemm.h; built by bnf_create in bnf_api.hip).
   const int32_t* fbmeta;
   int32_t off_lsa, n_groups, n_inputs, fb_in_group;   // fb_in_group: feature group of the raw inputs
   // q8 (compute_dtype 'fp8'): the copies this kernel leaves for the weight-gradient contractions are FP8 -- Hout[l] as OCP
@@ -123,7 +126,7 @@ struct PanelArgs {
 };
 constexpr float kW8Scale = 32.f;          // packed fp8 weights are K x 2^5 (|K| < 14 stays finite; e4m3 is normal down to 2^-6 / 32)
 constexpr int kW8ScaleE8M0 = 127 - 5;
-constexpr int kFbNone = 0, kFbInput = 1, kFbFourier = 2, kFbInter = 3;
+// (kFbNone / kFbInput / kFbFourier / kFbInter, the column kinds of fbmeta: bnf_gemm.h)
 
 // ---- fragment-major weight packing -------------------------------------------------
 // Wp[nt][ks][lane][8] : lane l of fragment (nt, ks) holds Bt[nt*32 + (l&31)][ks*16 + (l>>5)*8 + 0..7]
@@ -572,9 +575,16 @@ __device__ __forceinline__ void l0_mma(f32x16& a0, const L0Blk& bk) {
 // the ones column.  With no per-column constant left in the two layer-0 epilogues, both run with the MFMA operand
 // roles SWAPPED (weights as A, panel rows as B): a lane then owns ONE row and four consecutive hidden units per
 // register group, and the bf16 panel store is one ds_write_b64 per four elements instead of four ds_write_b16.
-template <int WN, int RT, bool H0L, bool DEEP = false, int CH = 1, int FP = 64, bool F0 = false, bool C8 = false>
+// FBW (needs H0L; StepPlan::featbwd_in_wgrad): the fused featurisation backward is formed by the layer-0 weight-gradient
+// kernel (gemm_tn_skinny_featbwd) from its own accumulators -- everything it needs from dH0 is linear in dZ0.  This kernel
+// then ENDS behind the dZ0 epilogue: no backward weight fragments of layer 0, no dH0 contraction, no column table, no
+// second barrier and no one-wave tail of global atomics.
+template <int WN, int RT, bool H0L, bool DEEP = false, int CH = 1, int FP = 64, bool F0 = false, bool C8 = false,
+          bool FBW = false>
 __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   static_assert(!F0 || H0L, "the folded layer 0 needs the LDS feature panel");
+  static_assert(!FBW || (H0L && !C8), "the featurisation backward moves to the bf16 layer-0 weight gradient of an H0L form");
+  const int32_t* const fbmeta = FBW ? nullptr : a.fbmeta;   // (FBW: every use of the column table compiles out)
   constexpr int W = 64 * WN * CH, RB = 8 / WN, WR = 32 * RT, BM = WR * RB;   // WR = rows per wave
   constexpr int kSlabs = WN * CH;           // 64-column slabs of the layer
   constexpr int kPitchE = W + 8;            // panel row pitch, elements (16 bytes of padding)
@@ -623,7 +633,7 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   const int LL = DEEP ? a.n_layers - 1 : 1; // index of the last hidden layer (1 for the two-layer networks)
   const float gamma0 = sc[0], gamma1 = sc[LL], alpha = sc[BNF_MAX_LAYERS];   // gamma1: the LAST hidden layer's scale
   const ActConst ak = act_const(alpha);
-  const float sp_in_u = (H0L && a.fbmeta) ? sc[kScalGroup + a.fb_in_group] : 1.f;   // softplus(scale of the raw-input group)
+  const float sp_in_u = (H0L && fbmeta) ? sc[kScalGroup + a.fb_in_group] : 1.f;   // softplus(scale of the raw-input group)
   const float inv_sw = 1.0f / sqrtf((float)a.Wt), inv_sf = 1.0f / sqrtf((float)a.F);
   float* gr = a.grad + (int64_t)e * a.grad_stride;
   // per-member scalars of the row phase and of the serial tails, fetched and transformed now (uniform):
@@ -658,10 +668,10 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   // dependent loads per group) and parked in LDS after the first phase: at the end of the panel the other
   // seven waves have nothing left to do while wave 0 finishes, so nothing there may wait for memory
   float g_fac = 0.f; int32_t g_off = 0;
-  if constexpr (H0L) {
+  if constexpr (H0L && !FBW) {
     if (tid < BNF_MAX_GROUPS + BNF_MAX_INPUTS) s_grp[tid] = 0.f;   // (ordered by the barriers of the phases below)
-    if (a.fbmeta && tid < a.n_groups) {   // two INDEPENDENT loads (the factor from the member's scalar table: a dependent
-      g_off = a.fbmeta[4 * FP + tid];     // th[g_off] here cost wave 0 a memory latency in front of its feature staging)
+    if (fbmeta && tid < a.n_groups) {   // two INDEPENDENT loads (the factor from the member's scalar table: a dependent
+      g_off = fbmeta[4 * FP + tid];     // th[g_off] here cost wave 0 a memory latency in front of its feature staging)
       g_fac = sc[kScalGfac + tid];
     }
   }
@@ -957,7 +967,7 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   }
   BNF_MARK(a, 1);
   if constexpr (H0L) {
-    if (a.fbmeta && tid < a.n_groups) { s_gfac[tid] = g_fac; s_goff[tid] = g_off; }
+    if (fbmeta && tid < a.n_groups) { s_gfac[tid] = g_fac; s_goff[tid] = g_off; }
   }
   PanelRing ring[CH];
   auto ring_prefetch = [&](const char* wp, int lane) {   // the first weight fragments of every slab of this wave
@@ -1808,6 +1818,34 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
       s_sc[33 + wave * 2] = sg0_all;
     }
   }
+  if constexpr (FBW) {
+    // the panel ends here: the barrier completes the column sums and scalars of the dZ0 epilogue, their atomics leave,
+    // and the layer-0 weight-gradient kernel forms the featurisation backward from the dZ0 copy already on its way
+    BNF_MARK(a, 12);
+    lds_barrier();
+    if constexpr (!F0) {
+      for (int c = tid; c < W; c += 512) {
+        float b = 0.f;
+#pragma unroll
+        for (int r = 0; r < RB; ++r) b += s_col[r * W + c];
+        atomicAdd(&gr[a.off_bias[0] + c], b);
+      }
+    }
+    if (tid == 0) {
+      float ta = ta1, tg = 0.f;
+#pragma unroll
+      for (int w2 = 0; w2 < 8; ++w2) {
+        ta += s_sc[32 + w2 * 2];
+        tg += s_sc[33 + w2 * 2];
+      }
+      atomicAdd(&gr[a.off_law], alpha * (1.f - alpha) * ta);
+      atomicAdd(&gr[a.off_ls[0]], dgam0 * tg);
+    }
+    BNF_MARK(a, 13);
+    BNF_MARK(a, 14);
+    BNF_MARK(a, 15);
+    return;
+  }
   int4 md_red = {0, 0, 0, 0};   // fused featurisation backward: column table entry of the final reduction (wave 0)
   // =============================== dH0^T = (dZ0 K0^T / sqrt F)^T ==============================
   // Output tiles of 32 x 32 over the waves.  All W/16 weight fragments of a tile are requested
@@ -1832,9 +1870,9 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
     // reduction (wave 0: one column per lane), in flight across the barrier like the weights
     int4 md_first = {0, 0, 0, 0};
     if constexpr (H0L) {
-      if (a.fbmeta) {
-        md_first = *reinterpret_cast<const int4*>(a.fbmeta + 4 * ((wave % ct) * 32 + frow));
-        if (wave < FP / 64) md_red = *reinterpret_cast<const int4*>(a.fbmeta + 4 * (wave * 64 + lane));
+      if (fbmeta) {
+        md_first = *reinterpret_cast<const int4*>(fbmeta + 4 * ((wave % ct) * 32 + frow));
+        if (wave < FP / 64) md_red = *reinterpret_cast<const int4*>(fbmeta + 4 * (wave * 64 + lane));
       }
     }
     BNF_MARK(a, 12);
@@ -1877,14 +1915,14 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
         }
       }
       if constexpr (H0L) {
-        if (a.fbmeta) {
+        if (fbmeta) {
           // featurisation backward on the tile: with H0 = softplus(scale_g) G,
           //   d scale_g            ~ sum_r dH0[r][f] H0[r][f]                       (every column of group g)
           //   d lsa_d (input / interaction columns)  ~ the same products
           //   d lsa_d (Fourier cos / sin column k)   ~ -+ 2 pi 2^k sum_r dH0[r][f] H0[r][partner] u_d[r],
           //                                            u_d = H0[r][input column d] / softplus(scale_in)
           const int f = ni * 32 + frow;
-          const int4 md = (t == wave) ? md_first : *reinterpret_cast<const int4*>(a.fbmeta + 4 * f);
+          const int4 md = (t == wave) ? md_first : *reinterpret_cast<const int4*>(fbmeta + 4 * f);
           const char* hc = h0s + (mi * 32 + 4 * kg) * kH0Pitch;
           const int o_f = f * 2, o_p = (md.y & 0xff) * 2, o_u = ((md.y >> 8) & 0xff) * 2;
           float s1 = 0.f, s2 = 0.f;
@@ -1918,7 +1956,7 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   }
   BNF_MARK(a, 13);
   if constexpr (H0L) {
-    if (a.fbmeta) {
+    if (fbmeta) {
       lds_barrier();
       if (wave < FP / 64) {                 // one feature column per lane
         const int f = wave * 64 + (opaque_lane(tid) & 63);

@@ -33,6 +33,7 @@ struct Switches {
   bool fp8_contract = true;      // BNF_FP8_CONTRACT=0: bf16 W x W contractions in the fp8 handle
   bool panel_fold0 = true;       // BNF_PANEL_FOLD0=0
   bool panel_featbwd = true;     // BNF_PANEL_FEATBWD=0
+  bool featbwd_wgrad = true;     // BNF_FEATBWD_WGRAD=0: the fused featurisation backward stays in the panel kernel
   bool panel_no_h0l = false;     // BNF_PANEL_NO_H0L (presence)
   bool overlap = false;          // BNF_OVERLAP=1: weight gradients on a side stream
   bool wgrad_no_multi = false;   // BNF_WGRAD_NO_MULTI (presence): one launch per W x W layer
@@ -58,6 +59,7 @@ inline Switches read_switches(Lookup&& lookup) {
   if ((v = lookup("BNF_FP8_CONTRACT"))) s.fp8_contract = atoi(v) != 0;
   if ((v = lookup("BNF_PANEL_FOLD0"))) s.panel_fold0 = atoi(v) != 0;
   if ((v = lookup("BNF_PANEL_FEATBWD"))) s.panel_featbwd = atoi(v) != 0;
+  if ((v = lookup("BNF_FEATBWD_WGRAD"))) s.featbwd_wgrad = atoi(v) != 0;
   s.panel_no_h0l = lookup("BNF_PANEL_NO_H0L") != nullptr;
   if ((v = lookup("BNF_OVERLAP"))) s.overlap = atoi(v) != 0;
   s.wgrad_no_multi = lookup("BNF_WGRAD_NO_MULTI") != nullptr;
@@ -71,6 +73,9 @@ inline Switches read_switches(Lookup&& lookup) {
 enum { WG_TN128 = 0, WG_TN256 = 1, WG_RING = 2, WG_SKINNY = 3 };   // weight-gradient kernels
 // tile sizes the plan counts with (bnf_api.hip asserts them equal to kBM, kBN and kSkRows of bnf_gemm.h)
 constexpr int kPlanBM = 128, kPlanBN = 128, kPlanSkRows = 32;
+// Fourier feature columns the layer-0 weight-gradient kernel can take the featurisation backward for: each becomes two
+// extra operand rows (bf16 hi + lo of a product of two features) beside the 64 feature rows (kSkFbCols of bnf_gemm.h)
+constexpr int kPlanFbCols = 32;
 
 // what the plan depends on, and nothing else
 struct PlanShape {
@@ -81,6 +86,9 @@ struct PlanShape {
   bool panel;         // row-panel pipeline
   bool pad;           // model width < W: gradients pass through a padded copy, nothing is kept
   int32_t off_kernel[BNF_MAX_LAYERS];   // offsets of the hidden Dense kernels in the parameter vector
+  bool fp8;           // the fp8 handle (dZ_0 leaves the panel kernel as e5m2)
+  bool featbwd_fused; // the panel kernel's fused featurisation backward is on (its column table exists)
+  int n_fourier;      // Fourier feature columns of the model
 };
 
 // Which kernel computes layer l's weight gradient and with what split-K (1: the kernel STORES dK_l, > 1: f32 atomics).
@@ -147,6 +155,9 @@ struct StepPlan {
   // VI (k_vi_adam): every layer with split-K 1.
   int n_keep;
   int32_t keep_lo[BNF_MAX_LAYERS], keep_hi[BNF_MAX_LAYERS];
+  // the fused featurisation backward is formed by the layer-0 weight-gradient kernel (gemm_tn_skinny_featbwd) from its
+  // own accumulators instead of by the last phase of the panel kernel, which then ends behind its dZ_0 epilogue
+  bool featbwd_in_wgrad;
 };
 
 // nmem: the members the step's kernels run over (members for MAP, members x samples for VI)
@@ -176,6 +187,9 @@ inline StepPlan make_step_plan(const PlanShape& ps, const Switches& sw, int nmem
       for (int i = 0; i < ps.L; ++i) p.launch[p.n_launch++] = sw.wgrad_order_fwd ? i : ps.L - 1 - i;
     }
   }
+
+  p.featbwd_in_wgrad = ps.panel && ps.bf16 && !ps.fp8 && ps.featbwd_fused && sw.panel_featbwd && sw.featbwd_wgrad &&
+                       ps.n_fourier <= kPlanFbCols && p.layer[0].kind == WG_SKINNY;
 
   if (!ps.pad && !sw.adam_clear_all && sw.ablate == 0) {
     for (int l = vi ? 0 : 1; l < ps.L; ++l) {
