@@ -94,13 +94,11 @@ static constexpr int64_t kAtPad = 128;
 struct bnf_handle {
   bnf_config cfg;
   Switches sw;     // the BNF_* environment, read once at bnf_create (bnf_plan.h)
-  StepPlan plan;   // weight-gradient kernels, their launch order and the optimiser's kept ranges: decided once, at bnf_create
+  StepPlan plan;   // weight-gradient kernels, their launch order and the optimiser's kept ranges
   NetDev nd;
   FreqTab ft;
   bool bf16 = false;
   int f32_split = 0;      // BNF_DTYPE_F32S: the f32 contractions on split-bf16 MFMAs (GemmArgs.f32_split)
-  bool q8 = false;        // BNF_DTYPE_FP8: bf16 contractions + fp8 operand copies for the weight-gradient kernels (bnf_gemm8.h)
-  bool c8 = false;        // ... and the W x W contractions of the two-layer MAP row-panel forms on the fp8 MFMA (PanelArgs.c8)
   uint8_t* Wf8[BNF_MAX_LAYERS] = {}; uint8_t* Wb8[BNF_MAX_LAYERS] = {};   // e4m3 x 2^5 K = 64 weight fragments (layers >= 1)
   uint8_t* H0q = nullptr; // (Ev, Bp, Fp) e4m3 copy of the features (layer-0 weight gradient)
   float* qscale = nullptr;   // (Ev) s_H s_dZ of the step: written by the panel kernel, read by the weight-gradient kernels
@@ -118,11 +116,7 @@ struct bnf_handle {
   int32_t* pad_src = nullptr;
   int32_t* fold_src = nullptr;
   std::vector<int32_t> pad_src_h, fold_src_h;
-  // row-panel kernel, H0L variant: per-column table of the fused featurisation backward (bnf_panel.h)
   int32_t* fbmeta = nullptr;
-  std::vector<int32_t> fbmeta_h;
-  int fb_in_group = -1;
-  int n_fourier = 0;          // Fourier feature columns of the model (StepPlan::featbwd_in_wgrad takes at most kSkFbCols)
   int64_t N = 0, B = 0, Bp = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;            // weight-gradient contractions overlap the dgrad chain
@@ -157,23 +151,18 @@ struct bnf_handle {
   size_t owned_bytes = 0;        // device memory the engine allocated itself (bnf_owned_bytes)
   int32_t* perm = nullptr; int64_t perm_epoch = -1;      // the current epoch's (members, N) row ids
   int32_t* leaf_off = nullptr; uint8_t* leaf_id = nullptr; int32_t n_leaves = 0;
-  bool h0l = false;
-  bool fold0 = false;   // the panel kernel's F0 forms: layer-0 scale / bias folded into its contraction (needs h0l, F + 2 <= Fp)
   void* A[BNF_MAX_LAYERS]; void* H[BNF_MAX_LAYERS];
   void* dZ[BNF_MAX_LAYERS];
   void* Kn[BNF_MAX_LAYERS]; void* Kt[BNF_MAX_LAYERS];
   int64_t pack_batch[BNF_MAX_LAYERS];
   float* dH0 = nullptr; float* out = nullptr; float* ybat = nullptr; float* loss_raw = nullptr;
   float* vacc = nullptr; float* dv = nullptr;   // output-layer dot accumulator, d loss / d v
-  bool panel = false;         // row-panel forward + backward kernel (bnf_panel.h): bf16, depth 2, W = 256 / 512
   void* Wf[BNF_MAX_LAYERS]; void* Wb[BNF_MAX_LAYERS];   // fragment-major packed weights
   void* park[BNF_MAX_LAYERS];                            // row-panel pipeline, depth > 2: parked pre-activations of the middle layers
     unsigned long long* prof_buf = nullptr;   // phase clocks (ABLATE builds)
   double prof_gap[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   double prof_blocks = 0;
   int prof_threads = 0;
-  bool recompute_a0 = false;  // layer-0 pre-activation recomputed in the backward pass (DGRAD TAG 2)
-  bool fuse_last = false;     // last layer + likelihood + its backward in one kernel (EPI_LAST)
   int num_cus = 256;          // multiProcessorCount of the device
   float* scal = nullptr;      // (Ev, kScalStride) transformed scalar leaves (k_member_scalars)
   StepState* step_state = nullptr;   // device: per-step state of the graph-replayed loop
@@ -191,15 +180,15 @@ struct bnf_handle {
   size_t pool_used = 0;
   double acc_ms[KID_COUNT];
   int64_t acc_calls[KID_COUNT];
+  // what bnf_create decided beside `plan` (bnf_plan.h)
+  PipelinePlan pp;       // the forward / backward pipeline and its flags
+  FeatBwdTable fb;       // row-panel kernel, H0L forms: per-column table of the fused featurisation backward (device copy: fbmeta)
+  PanelForm form;        // the row-panel kernel's instantiation ...
+  int form_index = -1;   // ... its row in kPanelForms / kPanelLaunch ...
+  int32_t panels = 0;    // ... and its workgroups per member: Bp / form.panel_rows
 };
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
-// the H0L panel forms (feature panel staged in LDS) exist for these shapes
-static bool panel_h0l(const bnf_handle* h) {
-  const bool shape = ((h->W == 512 || h->W == 1024) && h->Fp == 64) || (h->W == 256 && (h->Fp == 64 || h->Fp == 128));
-  return h->panel && shape && !h->sw.panel_no_h0l;
-}
 
 // carve or just measure (base == nullptr) the workspace layout
 static size_t carve(bnf_handle* h, char* base) {
@@ -224,29 +213,28 @@ static size_t carve(bnf_handle* h, char* base) {
   h->stab = (float*)take((size_t)std::max<int64_t>(1, h->N * nf2) * 4);
   h->stab_pred = (float*)take((size_t)std::max<int64_t>(1, Bp * nf2) * 4);
   h->H0 = take((size_t)Ev * Bp * Fp * es);
-  h->H0q = (h->q8 && !fo) ? (uint8_t*)take((size_t)Ev * Bp * Fp) : nullptr;
-  h->qscale = (h->q8 && !fo) ? (float*)take((size_t)Ev * 4) : nullptr;
+  h->H0q = (h->pp.q8 && !fo) ? (uint8_t*)take((size_t)Ev * Bp * Fp) : nullptr;
+  h->qscale = (h->pp.q8 && !fo) ? (float*)take((size_t)Ev * 4) : nullptr;
   // no transposed copies (the weight-gradient contraction reads row-major, gemm_tn); the row-panel
   // kernel reads the features as MFMA A fragments from a second, fragment-major copy (H0t slot)
-  // (the H0L variant -- W = 512, Fp = 64 -- stages the row-major copy in LDS instead and skips it)
-  h->h0l = panel_h0l(h);
-  h->H0t = (h->panel && !h->h0l) ? take((size_t)Ev * Bp * Fp * es) : nullptr;
+  // (the H0L forms stage the row-major copy in LDS instead and skip it)
+  h->H0t = (h->pp.panel && !h->pp.h0l) ? take((size_t)Ev * Bp * Fp * es) : nullptr;
   for (int l = 0; l < h->L; ++l) {
-    h->A[l] = (h->panel || (h->fuse_last && l == h->L - 1) || (h->recompute_a0 && l == 0)) ? nullptr : take((size_t)Ev * W * (Bp + kAtPad) * es);  // A_l^T (W, Bp + pad)
+    h->A[l] = (h->pp.panel || (h->pp.fuse_last && l == h->L - 1) || (h->pp.recompute_a0 && l == 0)) ? nullptr : take((size_t)Ev * W * (Bp + kAtPad) * es);  // A_l^T (W, Bp + pad)
     h->H[l] = (l < h->L - 1) ? take((size_t)Ev * Bp * W * es) : nullptr;       // H_{l+1} (Bp, W)
     h->dZ[l] = fo ? nullptr : take((size_t)Ev * Bp * W * es);
     const int64_t npad = (l == 0) ? Fp : W;
     h->pack_batch[l] = npad * W;
-    h->Kn[l] = h->panel ? nullptr : take((size_t)Ev * npad * W * es);
-    h->Kt[l] = h->panel ? nullptr : take((size_t)Ev * npad * W * es);
+    h->Kn[l] = h->pp.panel ? nullptr : take((size_t)Ev * npad * W * es);
+    h->Kt[l] = h->pp.panel ? nullptr : take((size_t)Ev * npad * W * es);
   }
   for (int l = 0; l < h->L; ++l) {
     const int64_t npad = (l == 0) ? Fp : W;
-    h->Wf[l] = h->panel ? take((size_t)Ev * npad * W * es) : nullptr;
-    h->Wb[l] = h->panel ? take((size_t)Ev * npad * W * es) : nullptr;
-    h->park[l] = (h->panel && !fo && l >= 1 && l < h->L - 1) ? take((size_t)Ev * Bp * W * es) : nullptr;
-    h->Wf8[l] = (h->c8 && l >= 1) ? (uint8_t*)take((size_t)Ev * W * W) : nullptr;
-    h->Wb8[l] = (h->c8 && l >= 1) ? (uint8_t*)take((size_t)Ev * W * W) : nullptr;
+    h->Wf[l] = h->pp.panel ? take((size_t)Ev * npad * W * es) : nullptr;
+    h->Wb[l] = h->pp.panel ? take((size_t)Ev * npad * W * es) : nullptr;
+    h->park[l] = (h->pp.panel && !fo && l >= 1 && l < h->L - 1) ? take((size_t)Ev * Bp * W * es) : nullptr;
+    h->Wf8[l] = (h->pp.c8 && l >= 1) ? (uint8_t*)take((size_t)Ev * W * W) : nullptr;
+    h->Wb8[l] = (h->pp.c8 && l >= 1) ? (uint8_t*)take((size_t)Ev * W * W) : nullptr;
   }
   h->dH0 = fo ? nullptr : (float*)take((size_t)Ev * Fp * Bp * 4);            // dH0^T (Fp, Bp)
   h->out = (float*)take((size_t)Ev * Bp * 4);
@@ -259,7 +247,7 @@ static size_t carve(bnf_handle* h, char* base) {
   h->step_state = (StepState*)take(sizeof(StepState));
   h->dbg_a = (float*)take(256);
   h->is_matrix = (uint8_t*)take((size_t)P);
-  h->fbmeta = h->fbmeta_h.empty() ? nullptr : (int32_t*)take(h->fbmeta_h.size() * 4);
+  h->fbmeta = h->fb.meta.empty() ? nullptr : (int32_t*)take(h->fb.meta.size() * 4);
   if (h->cfg.mode == BNF_MODE_VI) {
     h->leaf_off = (int32_t*)take(260 * 4);
     h->leaf_id = (uint8_t*)take((size_t)P);
@@ -416,11 +404,11 @@ static void launch_gemm(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep) {
   launch_gemm_wg<T, EPI, TAG, 2, 2>(h, kid, g, ep);
 }
 
-// Widths the one-kernel last layer (EPI_LAST: 128-row panels spanning the layer) supports.
-template <typename T>
-static bool fused_last_supported(int W) {
-  return W == 64 || W == 128 || W == 256 || (W == 512 && sizeof(T) == 2);
-}
+// The one-kernel last layer (EPI_LAST: 128-row panels spanning the layer): one case per width fused_last_width() of
+// bnf_plan.h admits -- PipelinePlan::fuse_last is on for no other
+static_assert(fused_last_width(64, false) && fused_last_width(128, false) && fused_last_width(256, false) && fused_last_width(512, true) &&
+              !fused_last_width(512, false) && !fused_last_width(1024, true) && !fused_last_width(192, true),
+              "launch_fwd_last_obs has a case for every width the plan fuses");
 template <typename T, int TAG>
 static void launch_fwd_last_obs(bnf_handle* h, GemmArgs g, const EpiArgs& ep) {
   switch (g.N) {
@@ -484,7 +472,7 @@ static void launch_gemm_tn_skinny_featbwd(bnf_handle* h, int kid, GemmArgs g, co
   fw.Wb0 = (const bf16_t*)h->Wb[0]; fw.wb_batch = h->pack_batch[0];
   fw.scal = h->scal; fw.fbmeta = h->fbmeta;
   fw.F = h->F; fw.off_lsa = h->nd.off_lsa; fw.n_groups = h->nd.n_groups; fw.n_inputs = h->nd.D;
-  fw.scal_stride = kScalStride; fw.scal_gfac = kScalGfac; fw.scal_sp_in = kScalGroup + h->fb_in_group;
+  fw.scal_stride = kScalStride; fw.scal_gfac = kScalGfac; fw.scal_sp_in = kScalGroup + h->fb.in_group;
   static std::atomic<uint64_t> attr_done{0};
   allow_lds(h, &gemm_tn_skinny_featbwd, kSkLdsFb, &attr_done);
   const unsigned blocks = (unsigned)((int64_t)g.members * g.tiles_n * g.splitk);
@@ -621,7 +609,7 @@ static void run_forward(bnf_handle* h, const float* theta, int nmem, const RowSr
                        (T*)nullptr, (int64_t)h->Fp * Bp, (int32_t)Bp,
                        train ? h->ybat : (float*)nullptr, Bp, (int32_t)nmem, (int32_t)0);
   }
-  const int n_layers = (train && h->fuse_last) ? h->L - 1 : h->L;   // EPI_LAST runs in run_backward
+  const int n_layers = (train && h->pp.fuse_last) ? h->L - 1 : h->L;   // EPI_LAST runs in run_backward
   for (int l = 0; l < n_layers; ++l) {
     const bool last = l == h->L - 1;
     GemmArgs g{};
@@ -650,9 +638,9 @@ static_assert(kPlanBM == kBM && kPlanBN == kBN && kPlanSkRows == kSkRows && kPla
 static PlanShape plan_shape(const bnf_handle* h) {
   PlanShape ps{};
   ps.bf16 = h->bf16; ps.L = h->L; ps.W = h->W; ps.F = h->F; ps.Fp = h->Fp; ps.Bp = h->Bp;
-  ps.num_cus = h->num_cus; ps.panel = h->panel; ps.pad = h->pad;
+  ps.num_cus = h->num_cus; ps.panel = h->pp.panel; ps.pad = h->pad;
   for (int l = 0; l < h->L; ++l) ps.off_kernel[l] = h->nd.off_kernel[l];
-  ps.fp8 = h->q8; ps.featbwd_fused = !h->fbmeta_h.empty(); ps.n_fourier = h->n_fourier;
+  ps.fp8 = h->pp.q8; ps.featbwd_fused = !h->fb.meta.empty(); ps.n_fourier = h->fb.n_fourier;
   return ps;
 }
 
@@ -672,11 +660,11 @@ static void run_wgrad_layer(bnf_handle* h, int nmem, int l, hipStream_t st) {
   EpiArgs ep{};
   ep.scale = 1.0f / sqrtf((float)((l == 0) ? h->F : h->Wt));
   ep.grad = h->gradf; ep.grad_stride = h->Pf; ep.off_out = h->nd.off_kernel[l]; ep.ld_f32 = h->W;
-  if (l == 0 && h->panel && h->fold0) {   // the ones column behind the features: its row of the product is d bias0
+  if (l == 0 && h->pp.fold0) {   // the ones column behind the features: its row of the product is d bias0
     ep.bias_row = 1; ep.off_bias_row = h->nd.off_bias[0];
   }
   if constexpr (sizeof(T) == 2) {
-    if (h->q8) {   // the fp8 copies: same shapes, one byte per element
+    if (h->pp.q8) {   // the fp8 copies: same shapes, one byte per element
       if (l == 0) g.A = h->H0q;
       ep.qscale = h->qscale;
       if (l == 0) launch_gemm_tn8<0>(h, KID_WGRAD0, g, ep, st, plan.kind);
@@ -729,7 +717,7 @@ static void run_wgrad_merged(bnf_handle* h, int nmem) {
   EpiArgs ep{};
   ep.scale = 1.0f / sqrtf((float)h->Wt);
   ep.grad = h->gradf; ep.grad_stride = h->Pf; ep.off_out = h->nd.off_kernel[1]; ep.ld_f32 = h->W;
-  if (h->q8) {
+  if (h->pp.q8) {
     ep.qscale = h->qscale;
     launch_gemm_tn8<1>(h, KID_WGRAD, g, ep, h->stream, WG_RING);
   } else {
@@ -751,7 +739,7 @@ static void run_backward(bnf_handle* h, const float* theta, int nmem, const RowS
                          int64_t rows, float c, const LossSink& sink) {
   const int64_t Bp = h->Bp;
   const int L = h->L;
-  if (h->fuse_last) {
+  if (h->pp.fuse_last) {
     // last hidden layer forward + output layer + likelihood + backward through its
     // activation in one kernel (EPI_LAST): writes out, dZ_{L-1} and every gradient the
     // row-loss and last-backward kernels produce
@@ -821,7 +809,7 @@ static void run_backward(bnf_handle* h, const float* theta, int nmem, const RowS
       ep.out_h = h->dZ[l - 1];
       ep.act_batch = Bp * h->W; ep.actt_batch = (int64_t)h->W * (Bp + kAtPad);
       ep.ld = h->W; ep.ldt = (int32_t)(Bp + kAtPad);
-      if (l == 1 && h->recompute_a0) {
+      if (l == 1 && h->pp.recompute_a0) {
         ep.aux_a = h->H0; ep.aux_a_batch = Bp * h->Fp;
         ep.aux_b = h->Kt[0]; ep.aux_b_batch = h->pack_batch[0];
         ep.aux_ld = h->Fp; ep.aux_scale = 1.0f / sqrtf((float)h->F);
@@ -864,7 +852,7 @@ static PackJobs pack_jobs(const bnf_handle* h, int* n_tiles) {
     jb.wf[l] = h->Wf[l]; jb.wb[l] = h->Wb[l]; jb.batch[l] = h->pack_batch[l];
   }
   jb.tile0[h->L] = tiles;
-  jb.fold0 = h->fold0 ? 1 : 0; jb.F0n = h->F; jb.off_bias0 = h->nd.off_bias[0]; jb.off_ls0 = h->nd.off_ls[0];
+  jb.fold0 = h->pp.fold0 ? 1 : 0; jb.F0n = h->F; jb.off_bias0 = h->nd.off_bias[0]; jb.off_ls0 = h->nd.off_ls[0];
   for (int l = 0; l < h->L; ++l) { jb.wf8[l] = h->Wf8[l]; jb.wb8[l] = h->Wb8[l]; }
   jb.batch8 = (int64_t)h->W * h->W;
   *n_tiles = tiles;
@@ -880,11 +868,11 @@ static void run_pack_fragments(bnf_handle* h, const float* theta, int nmem) {
 }
 
 // ---------------------------------------------------------------------------
-// row-panel pipeline (bf16, depth 2): pack fragments -> featurise -> k_panel_fwd_bwd ->
-// featurise backward -> gemm_tn weight gradients
+// row-panel pipeline (bf16 / fp8, depth >= 2): pack fragments -> featurise -> k_panel_fwd_bwd ->
+// featurise backward (where it is not fused) -> gemm_tn weight gradients
 // ---------------------------------------------------------------------------
-template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP, bool F0, bool C8 = false, bool FBW = false>
-static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
+template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP, bool F0, bool C8, bool FBW>
+static void launch_panel_form(bnf_handle* h, const PanelArgs& pa) {
   constexpr int kLds = panel_lds_bytes(WN, RT, H0L, CH, FP);
   static_assert(kLds <= 160 * 1024, "LDS per workgroup");
   static std::atomic<uint64_t> attr_done{0};
@@ -903,35 +891,14 @@ static void launch_panel_f(bnf_handle* h, const PanelArgs& pa) {
   }
   phase_prof_end(h, KID_PANEL, blocks, 512);
 }
-template <int WN, int RT, bool H0L, bool DEEP, int CH, int FP>
-static void launch_panel_d(bnf_handle* h, const PanelArgs& pa) {
-  if constexpr (H0L && WN == 8 && FP == 64) {
-    // the plan moved the featurisation backward into the layer-0 weight gradient (bf16, W = 512 / 1024, Fp = 64): the
-    // forms that end behind the dZ0 epilogue
-    if (h->plan.featbwd_in_wgrad) {
-      if (h->fold0) launch_panel_f<WN, RT, H0L, DEEP, CH, FP, true, false, true>(h, pa);
-      else launch_panel_f<WN, RT, H0L, DEEP, CH, FP, false, false, true>(h, pa);
-      return;
-    }
-  }
-  if constexpr (H0L) {
-    if (h->fold0) {
-      if (pa.c8) {      // fp8 W x W contractions: the folded forms (bnf_create decides h->c8)
-        launch_panel_f<WN, RT, H0L, DEEP, CH, FP, true, true>(h, pa);
-        return;
-      }
-      launch_panel_f<WN, RT, H0L, DEEP, CH, FP, true>(h, pa);
-      return;
-    }
-  }
-  launch_panel_f<WN, RT, H0L, DEEP, CH, FP, false>(h, pa);
-}
-
-template <int WN, int RT, bool H0L, int CH = 1, int FP = 64>
-static void launch_panel(bnf_handle* h, const PanelArgs& pa) {
-  if (pa.n_layers == 2) launch_panel_d<WN, RT, H0L, false, CH, FP>(h, pa);
-  else launch_panel_d<WN, RT, H0L, true, CH, FP>(h, pa);
-}
+// one launcher per row of kPanelForms (bnf_plan.h), in its order: h->form_index selects
+using PanelLaunch = void (*)(bnf_handle*, const PanelArgs&);
+#define BNF_PANEL_LAUNCH_ROW(WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW) &launch_panel_form<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW>,
+static const PanelLaunch kPanelLaunch[kNumPanelForms] = {BNF_PANEL_FORMS(BNF_PANEL_LAUNCH_ROW)};
+#undef BNF_PANEL_LAUNCH_ROW
+#define BNF_PANEL_ROWS_OK(WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW) && panel_rows(WN, RT) == 32 * RT * (8 / WN)
+static_assert(true BNF_PANEL_FORMS(BNF_PANEL_ROWS_OK), "PanelForm::panel_rows counts the kernel's rows per workgroup");
+#undef BNF_PANEL_ROWS_OK
 
 // fragments_packed: the caller has ALREADY written this step's weight fragments and scalar table (the VI sampler packs
 // while it samples: k_vi_sample_pack) -- an argument of this call, not handle state, so that no early return or partial
@@ -948,9 +915,8 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
     allow_lds(h, &k_featurize<bf16_t>, 160 * 1024, &attr_done);
     hipLaunchKernelGGL((k_featurize<bf16_t>), grid, dim3(kFeatRows), lds, h->stream, h->nd, rs, h->X, h->stab,
                        h->y, h->scal, h->B, (bf16_t*)h->H0, Bp * h->Fp, (bf16_t*)h->H0t,
-                       (int64_t)h->Fp * Bp, (int32_t)Bp, h->ybat, Bp, (int32_t)nmem, (int32_t)(h->fold0 ? 2 : 0), h->H0q);
+                       (int64_t)h->Fp * Bp, (int32_t)Bp, h->ybat, Bp, (int32_t)nmem, (int32_t)(h->pp.fold0 ? 2 : 0), h->H0q);
   }
-  bool feat_bwd_fused = false;
   PanelArgs pa{};
   pa.F = h->F; pa.Fp = h->Fp; pa.B = (int32_t)h->B; pa.members = nmem; pa.Wt = h->Wt;
   pa.theta = theta; pa.theta_stride = h->Pf; pa.scal = h->scal;
@@ -972,44 +938,16 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
   pa.grad = h->gradf; pa.grad_stride = h->Pf;
   pa.loss = sink.loss; pa.loss_raw = sink.raw; pa.loss_stride = sink.stride; pa.S = h->S;
   pa.loss_scale = sink.scale; pa.lik_c = c; pa.st = sink.st;
-  pa.q8 = h->q8 ? 1 : 0; pa.qscale = h->qscale;
-  pa.c8 = h->c8 ? 1 : 0; pa.w8_batch = (int64_t)h->W * h->W;
+  pa.q8 = h->pp.q8 ? 1 : 0; pa.qscale = h->qscale;
+  pa.c8 = h->pp.c8 ? 1 : 0; pa.w8_batch = (int64_t)h->W * h->W;
   for (int l = 0; l < L; ++l) { pa.Wf8[l] = h->Wf8[l]; pa.Wb8[l] = h->Wb8[l]; }
-  // 128-row panels at W = 512 (the feature panel staged in LDS when Fp = 64), 256-row panels at W = 256,
-  // 64-row panels with two 64-column slabs per wave at W = 1024
-  auto with_fused_featbwd = [&]() {
+  if (h->pp.h0l) {   // the fused featurisation backward (fbmeta null: no column table, k_feat_bwd below)
     pa.fbmeta = h->fbmeta; pa.off_lsa = h->nd.off_lsa; pa.n_groups = h->nd.n_groups; pa.n_inputs = h->nd.D;
-    pa.fb_in_group = h->fb_in_group;
-    feat_bwd_fused = h->fbmeta != nullptr;
-  };
-  if (h->W == 1024) {
-    pa.panels = (int32_t)(Bp / panel_rows(8, 2));
-    if (h->h0l) {
-      with_fused_featbwd();
-      launch_panel<8, 2, true, 2>(h, pa);
-    } else {
-      launch_panel<8, 2, false, 2>(h, pa);
-    }
-  } else if (h->W == 512) {
-    pa.panels = (int32_t)(Bp / panel_rows(8, 4));
-    if (h->h0l) {
-      with_fused_featbwd();
-      launch_panel<8, 4, true>(h, pa);
-    } else {
-      launch_panel<8, 4, false>(h, pa);
-    }
-  } else if (h->h0l) {
-    // W = 256 (C5: 65 .. 128 padded features; C1: 64): 128-row panels (two row blocks of 64) so that the feature panel
-    // (128 x 272 or 144 bytes) fits in LDS beside the activation panel; featurisation backward fused
-    pa.panels = (int32_t)(Bp / panel_rows(4, 2));
-    with_fused_featbwd();
-    if (h->Fp == 128) launch_panel<4, 2, true, 1, 128>(h, pa);
-    else launch_panel<4, 2, true, 1, 64>(h, pa);
-  } else {
-    pa.panels = (int32_t)(Bp / panel_rows(4, 4));
-    launch_panel<4, 4, false>(h, pa);
+    pa.fb_in_group = h->fb.in_group;
   }
-  if (!feat_bwd_fused)
+  pa.panels = h->panels;
+  kPanelLaunch[h->form_index](h, pa);
+  if (h->form.separate_feat_bwd)
   {
     LaunchScope ls(h, KID_FEATBWD);
     dim3 grid(cdiv(h->B, 256), (unsigned)nmem);
@@ -1172,7 +1110,7 @@ static int step_map(bnf_handle* h, int64_t epoch, int64_t step, const LossSink& 
   const int E = h->cfg.members;
   const float c = (float)((double)h->N / (double)h->B);
   const float* thf = fw_theta(h, h->params, E);
-  if (h->panel) {
+  if (h->pp.panel) {
     run_panel(h, thf, E, rs, c, sink);
   } else {
     run_pack<T>(h, thf, E);
@@ -1225,7 +1163,7 @@ static dim3 vi_sample_grid(const ViSegs& sg, int members) {
 // k_vi_sample_pack: row-panel pipeline on the parameter layout itself (no padded copy), every hidden kernel starting on
 // a quad boundary of the noise stream (always, with spec.py's layout), BNF_VI_SAMPLE_PACK=0 restores the two kernels
 static bool vi_sample_pack_ok(const bnf_handle* h) {
-  if (!h->sw.vi_sample_pack || !h->panel || h->pad || h->W % 64 != 0) return false;
+  if (!h->sw.vi_sample_pack || !h->pp.panel || h->pad || h->W % 64 != 0) return false;
   for (int l = 0; l < h->L; ++l)
     if ((h->nd.off_kernel[l] + kEpsQuadPhase) % 4 != 0) return false;
   return true;
@@ -1277,7 +1215,7 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
   const float c = (float)((double)h->N / (double)h->B / (double)kl);
   LossSink sink{loss, loss_stride, kl / (float)S, nullptr};
   const float* thf = fw_theta(h, h->theta_c, h->Ev);
-  if (h->panel) {
+  if (h->pp.panel) {
     run_panel(h, thf, h->Ev, rs, c, sink, /*fragments_packed=*/fused);
   } else {
     run_pack<T>(h, thf, h->Ev);
@@ -1445,7 +1383,6 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
   h->cfg = *cfg;
   h->bf16 = cfg->dtype == BNF_DTYPE_BF16 || cfg->dtype == BNF_DTYPE_FP8;   // (fp8: bf16 contractions, fp8 operand copies for the weight gradients)
   h->f32_split = cfg->dtype == BNF_DTYPE_F32S ? 2 : 0;
-  h->q8 = cfg->dtype == BNF_DTYPE_FP8;
   h->es = h->bf16 ? 2 : 4;
   h->S = S;
   h->Ev = cfg->members * S;
@@ -1453,7 +1390,7 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
   h->pad = h->W != h->Wt;
   h->F = cfg->n_features; h->P = cfg->n_params;
   h->Fp = (int)align_up(h->F, 64);
-  h->N = cfg->n_rows; h->B = cfg->batch; h->Bp = align_up(h->B, 128);
+  h->N = cfg->n_rows; h->B = cfg->batch;
   {
     // k_featurize stages kFeatRows rows of Fp (+ one 16-byte chunk) features in LDS
     const size_t feat_lds = (size_t)kFeatRows * (h->Fp + 16 / h->es) * h->es;
@@ -1535,92 +1472,33 @@ int bnf_create(const bnf_config* cfg, bnf_handle** out) {
   h->sw = read_switches(getenv);   // the one read of the environment: every switch belongs to the handle from here on
   h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   {
-    // 0 auto, 1 layer kernels with every activation materialised, 3 row-panel kernel
-    const int want = h->sw.pipeline_set ? h->sw.pipeline : cfg->pipeline;
-    if (want != 0 && want != 1 && want != 3) {
-      delete h;
-      return fail(BNF_ERR_INVALID, "pipeline %d (0 auto, 1 layers, 3 panel)", want);
-    }
-    // pipeline 3: row-panel forward + backward kernel (bf16, two hidden layers, width 256 / 512)
-    // pipeline 3: row-panel forward + backward kernel (bf16, >= 2 hidden layers, width 256 / 512): rows stay in LDS /
-    // registers through ALL layers; the middle layers of deeper networks park their pre-activations in HBM
-    const bool can_panel = !cfg->forward_only && h->bf16 && h->L >= 2 && (h->W == 256 || h->W == 512 || h->W == 1024) && h->Fp <= 128;
-    if (want == 3 && !can_panel) {
-      delete h;
-      return fail(BNF_ERR_INVALID, "panel pipeline needs a bf16 training handle with depth >= 2, width 256/512/1024 and <= 128 features");
-    }
-    h->panel = can_panel && (want == 3 || want == 0);   // the default where it applies (C2: 2.71 -> 2.27 ms/step)
-    if (h->q8 && !h->panel && !cfg->forward_only) {
-      delete h;
-      return fail(BNF_ERR_INVALID, "dtype fp8 (fp8 operand storage for the weight gradients) needs the row-panel pipeline: "
-                  "depth >= 2, width 256 / 512 / 1024 after padding to 64, <= 128 padded features");
-    }
-    if (h->panel) h->Bp = align_up(h->B, 256);
-    // fp8 W x W contractions (PanelArgs.c8): every folded row-panel form (W = 256 / 512 / 1024, any depth >= 2);
-    // BNF_FP8_CONTRACT=0 keeps the round-5 arithmetic (bf16 contractions, fp8 copies only)
-    h->c8 = h->q8 && h->panel && h->sw.fp8_contract;
-    // pipeline 0 (auto): layer kernels with the one-kernel last layer where the width allows;
-    // pipeline 1: every layer kernel separate and every activation materialised (validation)
-    const bool fl_ok = h->bf16 ? fused_last_supported<bf16_t>(h->W) : fused_last_supported<float>(h->W);
-    h->fuse_last = !cfg->forward_only && !h->panel && want == 0 && fl_ok;
-    // its contraction depth is Fp <= 128: cheaper to redo than to write + gather A_0^T
-    h->recompute_a0 = !cfg->forward_only && !h->panel && want == 0 && h->L >= 2 && h->Fp <= 128;
-  }
-  h->h0l = panel_h0l(h);
-  h->fold0 = h->h0l && h->F + 2 <= h->Fp && h->sw.panel_fold0;
-  h->c8 = h->c8 && h->fold0;     // (the fp8-contraction kernels are instantiated for the folded forms: every BASELINE layout)
-  if (h->h0l && h->sw.panel_featbwd) {
-    // fused featurisation backward of the H0L panel kernel: what each feature column contributes
-    int in_group = -1;
-    for (int g = 0; g < cfg->n_groups; ++g)
-      if (cfg->group_kind[g] == BNF_GROUP_INPUT) in_group = g;
-    if (in_group >= 0) {
-      std::vector<int32_t>& m = h->fbmeta_h;
-      const int Fp = h->Fp;                 // 64 or 128 (h0l); the group offsets follow the column entries
-      // ... and the slots of the Fourier columns (FeatBwdArgs::fbmeta: the layer-0 weight gradient's extra operand rows)
-      m.assign(Fp * 4 + BNF_MAX_GROUPS + kSkFbCols, 0);
-      auto put = [&](int col, int kind, int g, int d1, int d2, int partner, int ucol, float coef) {
-        m[4 * col] = kind | (g << 8) | (d1 << 16) | (d2 << 24);
-        m[4 * col + 1] = partner | (ucol << 8);
-        memcpy(&m[4 * col + 2], &coef, 4);
-      };
-      for (int c = 0; c < Fp; ++c) put(c, kFbNone, 0xff, 0xff, 0xff, 0, 0, 0.f);
-      const int cin = cfg->group_col0[in_group];
-      for (int g = 0; g < cfg->n_groups; ++g) {
-        const int c0 = cfg->group_col0[g], nc = cfg->group_ncols[g];
-        m[4 * Fp + g] = cfg->group_scale_off[g];
-        switch (cfg->group_kind[g]) {
-          case BNF_GROUP_INPUT:
-            for (int d = 0; d < nc; ++d) put(c0 + d, kFbInput, g, d, 0xff, 0, 0, 0.f);
-            break;
-          case BNF_GROUP_FOURIER: {
-            const int deg = nc / 2, d = cfg->group_arg[g];
-            for (int k = 0; k < deg; ++k) {
-              const float w = 6.28318530717958647692f * (float)(1u << k);
-              put(c0 + k, kFbFourier, g, d, 0xff, c0 + deg + k, cin + d, -w);
-              put(c0 + deg + k, kFbFourier, g, d, 0xff, c0 + k, cin + d, w);
-            }
-            break;
-          }
-          case BNF_GROUP_SEASONAL:
-            for (int j = 0; j < nc; ++j) put(c0 + j, kFbNone, g, 0xff, 0xff, 0, 0, 0.f);
-            break;
-          default:
-            for (int k = 0; k < nc; ++k)
-              put(c0 + k, kFbInter, g, cfg->interact[k][0], cfg->interact[k][1], 0, 0, 0.f);
-        }
-      }
-      h->fb_in_group = in_group;
-      h->n_fourier = 0;
-      for (int c = 0; c < Fp; ++c) {
-        if ((m[4 * c] & 0xff) != kFbFourier) continue;
-        if (h->n_fourier < kSkFbCols && Fp == 64)
-          m[4 * Fp + BNF_MAX_GROUPS + h->n_fourier] = c | ((m[4 * c + 1] & 0xffff) << 8) | (1 << 24);
-        ++h->n_fourier;
-      }
+    bool input_group = false;
+    for (int g = 0; g < cfg->n_groups; ++g) input_group = input_group || cfg->group_kind[g] == BNF_GROUP_INPUT;
+    h->pp = make_pipeline_plan({cfg->dtype, cfg->forward_only != 0, h->L, h->W, h->F, h->Fp, cfg->pipeline, input_group}, h->sw);
+    const PipelineRefusal refusal = h->pp.refusal;
+    const int want = h->sw.pipeline_set ? h->sw.pipeline : cfg->pipeline;   // (the value the message names)
+    if (refusal != PIPE_OK) delete h;
+    switch (refusal) {
+      case PIPE_OK: break;
+      case PIPE_BAD_VALUE: return fail(BNF_ERR_INVALID, "pipeline %d (0 auto, 1 layers, 3 panel)", want);
+      case PIPE_NO_PANEL:
+        return fail(BNF_ERR_INVALID, "panel pipeline needs a bf16 training handle with depth >= 2, width 256/512/1024 and <= 128 features");
+      case PIPE_FP8_NEEDS_PANEL:
+        return fail(BNF_ERR_INVALID, "dtype fp8 (fp8 operand storage for the weight gradients) needs the row-panel pipeline: "
+                    "depth >= 2, width 256 / 512 / 1024 after padding to 64, <= 128 padded features");
     }
   }
-  h->plan = make_step_plan(plan_shape(h), h->sw, h->Ev, cfg->mode == BNF_MODE_VI);   // (num_cus, panel and Bp are final)
+  // the plans, each from the ones before it (bnf_plan.h): pipeline -> Bp -> column table -> weight gradients -> panel form
+  h->Bp = align_up(h->B, h->pp.bp_align);
+  if (h->pp.fb_table)
+    h->fb = make_featbwd_table(cfg->n_groups, cfg->group_kind, cfg->group_arg, cfg->group_ncols, cfg->group_col0,
+                               cfg->group_scale_off, cfg->interact, h->Fp);
+  h->plan = make_step_plan(plan_shape(h), h->sw, h->Ev, cfg->mode == BNF_MODE_VI);
+  if (h->pp.panel) {
+    h->form = make_panel_form(h->pp, h->plan, h->L, h->W, h->Fp);
+    h->form_index = panel_form_index(h->form);
+    h->panels = (int32_t)(h->Bp / h->form.panel_rows);
+  }
   h->ws_bytes = carve(h, nullptr);
   *out = h;
   return BNF_OK;
@@ -1691,7 +1569,7 @@ int bnf_bind(bnf_handle* h, void* params, void* opt_state, void* workspace, cons
   }
   HIPCHK(hipMemcpyAsync(h->is_matrix, mm.data(), (size_t)h->P, hipMemcpyHostToDevice, h->stream));
   if (h->fbmeta)
-    HIPCHK(hipMemcpyAsync(h->fbmeta, h->fbmeta_h.data(), h->fbmeta_h.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->fbmeta, h->fb.meta.data(), h->fb.meta.size() * 4, hipMemcpyHostToDevice, h->stream));
   if (h->pad) {
     HIPCHK(hipMemcpyAsync(h->pad_src, h->pad_src_h.data(), h->pad_src_h.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->fold_src, h->fold_src_h.data(), h->fold_src_h.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -1867,7 +1745,7 @@ int bnf_forward(bnf_handle* h, const float* theta, int64_t n_members, const floa
                 int64_t n_rows, float* loc, float* aux) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "bnf_forward before bnf_bind");
   if (!theta || !Xnew || !loc || n_members < 1 || n_rows < 1) return fail(BNF_ERR_INVALID, "argument");
-  if (h->panel) return fail(BNF_ERR_STATE, "bnf_forward needs a forward_only (or pipeline=1) handle");
+  if (h->pp.panel) return fail(BNF_ERR_STATE, "bnf_forward needs a forward_only (or pipeline=1) handle");
   HIPCHK(hipSetDevice(h->cfg.device));
   const int64_t row_chunk = h->Bp, mem_chunk = h->Ev;
   RowSrc rs{};
@@ -2788,7 +2666,7 @@ int bnf_debug_activation(bnf_handle* h, int32_t what, float* out) {
   }
   if (!src) return fail(BNF_ERR_STATE, "buffer not allocated on this handle");
   dim3 grid(cdiv(B * cols, 256), (unsigned)h->Ev);
-  if (h->q8 && h->panel && what != 0) {   // the fp8 copies: H_l e4m3 un-scaled, dZ_l e5m2 x qscale[member]
+  if (h->pp.q8 && h->pp.panel && what != 0) {   // the fp8 copies: H_l e4m3 un-scaled, dZ_l e5m2 x qscale[member]
     const bool dz = what >= 300;
     hipLaunchKernelGGL(k_q8_to_f32, grid, dim3(256), 0, h->stream, (const uint8_t*)src, batch, ld, B, cols, out,
                        dz ? 1 : 0, dz ? h->qscale : (const float*)nullptr);
@@ -2855,7 +2733,7 @@ int bnf_debug_gemm_tn(bnf_handle* h, const float* A, const float* B, int32_t R, 
   g.A = dA; g.B = dB; g.a_ld = M; g.b_ld = N; g.M = M; g.N = N; g.K = R; g.splitk = 1; g.members = 1;
   EpiArgs ep{};
   ep.scale = 1.f; ep.out_f32 = C; ep.f32_batch = 0; ep.ld_f32 = N;
-  if (h->q8) {
+  if (h->pp.q8) {
     // A -> e4m3, B -> e5m2 (saturating, round to nearest even), then the fp8 kernel of the kind BNF_DEBUG_TN_KIND names
     // (0: the generic 128 x 128 tile, 2: ring -- M, N multiples of 256 --, 3: skinny -- M = 64, N a multiple of 512),
     // split-K BNF_DEBUG_TN_SPLITK: tests/test_gpu_fp8.py checks every kernel against the host product of the same
@@ -3125,7 +3003,7 @@ double bnf_kernel_flops(const bnf_handle* h, const char* name) {
   const double Ev = h->Ev, B = (double)h->B, W = h->Wt, F = h->F;
   // featbwd_in_wgrad: the panel kernel no longer contracts dH0 (below); the layer-0 weight gradient contracts the
   // 2 x n_fourier rows of G (bf16 hi + lo) beside the F feature rows
-  if (!strcmp(name, "gemm_wgrad_l0") && h->plan.featbwd_in_wgrad) return 2.0 * Ev * B * (F + 2.0 * h->n_fourier) * W;
+  if (!strcmp(name, "gemm_wgrad_l0") && h->plan.featbwd_in_wgrad) return 2.0 * Ev * B * (F + 2.0 * h->fb.n_fourier) * W;
   if (!strcmp(name, "gemm_fwd_l0") || !strcmp(name, "gemm_dgrad0") || !strcmp(name, "gemm_wgrad_l0"))
     return 2.0 * Ev * B * F * W;
   if (!strcmp(name, "gemm_wgrad") && h->plan.merged)   // one launch for the layers 1 .. L-1

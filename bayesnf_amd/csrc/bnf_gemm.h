@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "bnf_device.h"
+#include "bnf_plan.h"   // kFbNone .. kFbInter, the column kinds of the featurisation-backward table
 
 namespace bnf {
 
@@ -1360,7 +1361,6 @@ struct FeatBwdArgs {
   int32_t F, off_lsa, n_groups, n_inputs;
   int32_t scal_stride, scal_gfac, scal_sp_in;   // kScalStride, kScalGfac, kScalGroup + the raw-input group (bnf_kernels.h)
 };
-constexpr int kFbNone = 0, kFbInput = 1, kFbFourier = 2, kFbInter = 3;   // column kinds of the table
 __device__ __forceinline__ uint32_t lds_read_u16_asm(uint32_t addr) {
   uint32_t v;
   asm volatile("ds_read_u16 %0, %1" : "=v"(v) : "v"(addr) : "memory");

@@ -110,7 +110,7 @@ struct PanelArgs {
   // one instruction per element pair, half the store instructions and bytes).
   int32_t q8;
   float* qscale;
-  // c8 (round 6; compute_dtype 'fp8', the folded two-layer forms): the two W x W contractions of the panel run on the
+  // c8 (round 6; compute_dtype 'fp8', every folded form -- any depth >= 2, MAP and VI, W = 256 / 512 / 1024): the W x W contractions of the panel run on the
   // block-scaled fp8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4: K = 64 per instruction at twice the bf16 rate) -- weights
   // pre-packed as OCP e4m3 x 2^5 in K = 64 fragments (Wf8 / Wb8, k_pack_layers; the 2^-5 rides in the instruction's E8M0
   // scale), and the panels those contractions read live in LDS AS FP8 (row pitch W + 16 bytes): H_1 as e4m3, written by the
@@ -126,7 +126,7 @@ struct PanelArgs {
 };
 constexpr float kW8Scale = 32.f;          // packed fp8 weights are K x 2^5 (|K| < 14 stays finite; e4m3 is normal down to 2^-6 / 32)
 constexpr int kW8ScaleE8M0 = 127 - 5;
-// (kFbNone / kFbInput / kFbFourier / kFbInter, the column kinds of fbmeta: bnf_gemm.h)
+// (kFbNone / kFbInput / kFbFourier / kFbInter, the column kinds of fbmeta: bnf_plan.h, through bnf_gemm.h)
 
 // ---- fragment-major weight packing -------------------------------------------------
 // Wp[nt][ks][lane][8] : lane l of fragment (nt, ks) holds Bt[nt*32 + (l&31)][ks*16 + (l>>5)*8 + 0..7]
@@ -523,7 +523,7 @@ __device__ __forceinline__ void panel_contract8(f32x16 (&acc)[RT][2], const char
       }
     __builtin_amdgcn_sched_barrier(0);
   };
-  // (KS64 is even: W = 256 / 512) two k steps per trip so that the fragment buffers alternate without copies
+  // (KS64 is even: W = 256 / 512 / 1024, asserted where this is instantiated) two k steps per trip so that the fragment buffers alternate without copies
   step(0, std::true_type{}, std::integral_constant<int, 0>{});
   step(1, std::false_type{}, std::integral_constant<int, 1>{});
 #pragma unroll 1
@@ -976,6 +976,7 @@ __global__ __launch_bounds__(512, 2) void k_panel_fwd_bwd(const PanelArgs a) {
   };
   // c8: the W x W contraction on the fp8 MFMA (panel_contract8) out of the fp8 panel image; bf8: backward signals (e5m2 / s_dZ)
   auto contract_all8 = [&](const uint8_t* wp8, auto swap_tag, auto bf8_tag) {
+    static_assert(W / 64 >= 2 && (W / 64) % 2 == 0, "panel_contract8 takes its K = 64 steps in pairs");
     constexpr bool kBf8 = decltype(bf8_tag)::value;
     const int lane = opaque_lane(tid) & 63;
     const char* prow8 = smem + (rbase + (lane & 31)) * kPitch8 + (lane >> 5) * 32;

@@ -1,6 +1,8 @@
-// bnf_plan.h -- what a handle decides ONCE, at bnf_create: the environment switches (Switches) and the weight-gradient
-// side of the training step (StepPlan).  Host only, plain C++17, no HIP headers: tests/test_step_plan_host.py compiles
-// this file with g++ and asserts the plans without a GPU.
+// bnf_plan.h -- what a handle decides ONCE, at bnf_create: the environment switches (Switches), the forward / backward
+// pipeline (PipelinePlan), the column table of the fused featurisation backward (FeatBwdTable), the weight-gradient side
+// of the training step (StepPlan) and the instantiation of the row-panel kernel (PanelForm), in that order: each reads
+// the ones before it.  Host only, plain C++17, no HIP headers: tests/test_step_plan_host.py and
+// tests/test_pipeline_plan_host.py compile this file with g++ and assert the plans without a GPU.
 //
 // The step functions of bnf_api.hip execute h->plan; nothing on the step path reads the environment or derives a
 // kernel choice again.  The launcher and the optimiser therefore cannot disagree about which gradient ranges the next
@@ -11,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/bnf.h"
 
@@ -69,13 +72,124 @@ inline Switches read_switches(Lookup&& lookup) {
   return s;
 }
 
-// ---- the weight-gradient plan --------------------------------------------------------------------------------
-enum { WG_TN128 = 0, WG_TN256 = 1, WG_RING = 2, WG_SKINNY = 3 };   // weight-gradient kernels
 // tile sizes the plan counts with (bnf_api.hip asserts them equal to kBM, kBN and kSkRows of bnf_gemm.h)
 constexpr int kPlanBM = 128, kPlanBN = 128, kPlanSkRows = 32;
 // Fourier feature columns the layer-0 weight-gradient kernel can take the featurisation backward for: each becomes two
 // extra operand rows (bf16 hi + lo of a product of two features) beside the 64 feature rows (kSkFbCols of bnf_gemm.h)
 constexpr int kPlanFbCols = 32;
+
+// ---- the pipeline plan ---------------------------------------------------------------------------------------
+// Row-panel kernel (bnf_panel.h: rows stay in LDS / registers through ALL layers) or the layer kernels.
+struct PipelineShape {
+  int dtype;             // BNF_DTYPE_*
+  bool forward_only;
+  int L, W, F, Fp;       // hidden layers, width the kernels run at (the model's, padded to 64), features, padded features
+  int pipeline;          // bnf_config.pipeline: 0 auto, 1 layer kernels with every activation materialised, 3 row-panel kernel
+  bool input_group;      // the model has a raw-input feature group (the fused featurisation backward scales by its leaf)
+};
+enum PipelineRefusal { PIPE_OK = 0, PIPE_BAD_VALUE, PIPE_NO_PANEL, PIPE_FP8_NEEDS_PANEL };   // bnf_create: BNF_ERR_INVALID
+struct PipelinePlan {
+  PipelineRefusal refusal;
+  bool panel;           // row-panel forward + backward kernel: a bf16 / fp8 training handle, depth >= 2, W = 256 / 512 / 1024, Fp <= 128
+  bool fuse_last;       // layer kernels: last layer + likelihood + its backward in one kernel (EPI_LAST)
+  bool recompute_a0;    // layer kernels: layer-0 pre-activation recomputed in the backward pass (DGRAD TAG 2)
+  bool h0l;             // panel kernel: the feature panel staged in LDS (no fragment-major copy H0t)
+  bool fold0;           // panel kernel's F0 forms: layer-0 scale / bias folded into its contraction
+  bool q8;              // BNF_DTYPE_FP8: bf16 contractions + fp8 operand copies for the weight-gradient kernels (bnf_gemm8.h)
+  bool c8;              // ... and the W x W contractions of the folded row-panel forms on the fp8 MFMA (PanelArgs.c8)
+  bool fb_table;        // the column table of the fused featurisation backward is built (make_featbwd_table)
+  int bp_align;         // the batch is padded to a multiple of this many rows
+};
+// widths the one-kernel last layer has an instantiation for (launch_fwd_last_obs of bnf_api.hip)
+constexpr bool fused_last_width(int W, bool bf16) { return W == 64 || W == 128 || W == 256 || (W == 512 && bf16); }
+inline PipelinePlan make_pipeline_plan(const PipelineShape& s, const Switches& sw) {
+  PipelinePlan p{};
+  const bool bf16 = s.dtype == BNF_DTYPE_BF16 || s.dtype == BNF_DTYPE_FP8;
+  p.q8 = s.dtype == BNF_DTYPE_FP8;
+  p.bp_align = 128;
+  const int want = sw.pipeline_set ? sw.pipeline : s.pipeline;   // BNF_PIPELINE overrides the config
+  if (want != 0 && want != 1 && want != 3) { p.refusal = PIPE_BAD_VALUE; return p; }
+  const bool can_panel = !s.forward_only && bf16 && s.L >= 2 && (s.W == 256 || s.W == 512 || s.W == 1024) && s.Fp <= 128;
+  if (want == 3 && !can_panel) { p.refusal = PIPE_NO_PANEL; return p; }
+  p.panel = can_panel && want != 1;   // the default where it applies (C2: 2.71 -> 2.27 ms/step)
+  if (p.q8 && !p.panel && !s.forward_only) { p.refusal = PIPE_FP8_NEEDS_PANEL; return p; }
+  if (p.panel) p.bp_align = 256;
+  // pipeline 0 (auto): the one-kernel last layer where the width allows; 1: every activation materialised (validation)
+  const bool layers_auto = !s.forward_only && !p.panel && want == 0;
+  p.fuse_last = layers_auto && fused_last_width(s.W, bf16);
+  // its contraction depth is Fp <= 128: cheaper to redo than to write + gather A_0^T
+  p.recompute_a0 = layers_auto && s.L >= 2 && s.Fp <= 128;
+  // the H0L panel forms exist for these shapes; F0 needs two spare feature columns (the ones column and its partner)
+  const bool h0l_shape = ((s.W == 512 || s.W == 1024) && s.Fp == 64) || (s.W == 256 && (s.Fp == 64 || s.Fp == 128));
+  p.h0l = p.panel && h0l_shape && !sw.panel_no_h0l;
+  p.fold0 = p.h0l && s.F + 2 <= s.Fp && sw.panel_fold0;
+  // (the fp8-contraction kernels are instantiated for the folded forms; BNF_FP8_CONTRACT=0: the fp8 copies only)
+  p.c8 = p.q8 && p.fold0 && sw.fp8_contract;
+  p.fb_table = p.h0l && sw.panel_featbwd && s.input_group;
+  return p;
+}
+
+// ---- the column table of the fused featurisation backward ----------------------------------------------------
+// What each feature column contributes to the gradients of the feature scales and the raw-input scale: read by the H0L
+// panel kernel (PanelArgs::fbmeta, bnf_panel.h) and by gemm_tn_skinny_featbwd (FeatBwdArgs::fbmeta, bnf_gemm.h).
+//   words 4 c .. 4 c + 2 of column c: kind | group << 8 | d1 << 16 | d2 << 24;  partner column | input column << 8;  coefficient
+//   words 4 Fp + g: the scale leaf of group g;  words 4 Fp + BNF_MAX_GROUPS + q (Fp = 64): slot q = f | p << 8 | u << 16 |
+//   1 << 24 of the q-th Fourier column, the layer-0 weight gradient's extra operand rows (0: no such column)
+constexpr int kFbNone = 0, kFbInput = 1, kFbFourier = 2, kFbInter = 3;   // column kinds
+struct FeatBwdTable {
+  std::vector<int32_t> meta;   // empty: no table (PipelinePlan::fb_table is off)
+  int in_group = -1;           // the raw-input group
+  int n_fourier = 0;           // Fourier feature columns of the model (StepPlan::featbwd_in_wgrad takes at most kPlanFbCols)
+};
+inline FeatBwdTable make_featbwd_table(int n_groups, const int32_t* kind, const int32_t* arg, const int32_t* ncols,
+                                       const int32_t* col0, const int32_t* scale_off, const int32_t (*interact)[2], int Fp) {
+  FeatBwdTable t;
+  for (int g = 0; g < n_groups; ++g)
+    if (kind[g] == BNF_GROUP_INPUT) t.in_group = g;
+  if (t.in_group < 0) return t;
+  std::vector<int32_t>& m = t.meta;
+  m.assign(Fp * 4 + BNF_MAX_GROUPS + kPlanFbCols, 0);
+  auto put = [&](int col, int knd, int g, int d1, int d2, int partner, int ucol, float coef) {
+    m[4 * col] = knd | (g << 8) | (d1 << 16) | (d2 << 24);
+    m[4 * col + 1] = partner | (ucol << 8);
+    memcpy(&m[4 * col + 2], &coef, 4);
+  };
+  for (int c = 0; c < Fp; ++c) put(c, kFbNone, 0xff, 0xff, 0xff, 0, 0, 0.f);
+  const int cin = col0[t.in_group];
+  for (int g = 0; g < n_groups; ++g) {
+    const int c0 = col0[g], nc = ncols[g];
+    m[4 * Fp + g] = scale_off[g];
+    switch (kind[g]) {
+      case BNF_GROUP_INPUT:
+        for (int d = 0; d < nc; ++d) put(c0 + d, kFbInput, g, d, 0xff, 0, 0, 0.f);
+        break;
+      case BNF_GROUP_FOURIER: {
+        const int deg = nc / 2, d = arg[g];
+        for (int k = 0; k < deg; ++k) {
+          const float w = 6.28318530717958647692f * (float)(1u << k);
+          put(c0 + k, kFbFourier, g, d, 0xff, c0 + deg + k, cin + d, -w);
+          put(c0 + deg + k, kFbFourier, g, d, 0xff, c0 + k, cin + d, w);
+        }
+        break;
+      }
+      case BNF_GROUP_SEASONAL:
+        for (int j = 0; j < nc; ++j) put(c0 + j, kFbNone, g, 0xff, 0xff, 0, 0, 0.f);
+        break;
+      default:
+        for (int k = 0; k < nc; ++k) put(c0 + k, kFbInter, g, interact[k][0], interact[k][1], 0, 0, 0.f);
+    }
+  }
+  for (int c = 0; c < Fp; ++c) {
+    if ((m[4 * c] & 0xff) != kFbFourier) continue;
+    if (t.n_fourier < kPlanFbCols && Fp == 64)
+      m[4 * Fp + BNF_MAX_GROUPS + t.n_fourier] = c | ((m[4 * c + 1] & 0xffff) << 8) | (1 << 24);
+    ++t.n_fourier;
+  }
+  return t;
+}
+
+// ---- the weight-gradient plan --------------------------------------------------------------------------------
+enum { WG_TN128 = 0, WG_TN256 = 1, WG_RING = 2, WG_SKINNY = 3 };   // weight-gradient kernels
 
 // what the plan depends on, and nothing else
 struct PlanShape {
@@ -203,5 +317,78 @@ inline StepPlan make_step_plan(const PlanShape& ps, const Switches& sw, int nmem
   }
   return p;
 }
+
+// ---- the form of the row-panel kernel ------------------------------------------------------------------------
+// The template arguments of k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW> (bnf_panel.h) a handle launches: 128-row
+// panels at W = 512, 64-row panels of two column slabs at W = 1024, 128-row (H0L) or 256-row panels at W = 256.
+struct PanelForm {
+  int WN, RT; bool H0L, DEEP; int CH, FP; bool F0, C8, FBW;
+  int panel_rows;           // rows per workgroup: Bp / panel_rows workgroups per member
+  bool separate_feat_bwd;   // k_feat_bwd runs behind the panel kernel (no column table: nothing fused)
+};
+constexpr PanelForm make_panel_form(const PipelinePlan& pp, const StepPlan& sp, int L, int W, int Fp) {
+  PanelForm f{};
+  f.H0L = pp.h0l; f.DEEP = L != 2; f.CH = 1; f.FP = 64;
+  if (W == 1024) { f.WN = 8; f.RT = 2; f.CH = 2; }
+  else if (W == 512) { f.WN = 8; f.RT = 4; }
+  else if (pp.h0l) { f.WN = 4; f.RT = 2; f.FP = Fp == 128 ? 128 : 64; }
+  else { f.WN = 4; f.RT = 4; }
+  // FBW: the featurisation backward moved into the layer-0 weight gradient, the panel kernel ends behind its dZ0 epilogue
+  f.FBW = f.H0L && f.WN == 8 && sp.featbwd_in_wgrad;
+  f.F0 = pp.fold0;
+  f.C8 = pp.c8;
+  f.panel_rows = 32 * f.RT * (8 / f.WN);
+  f.separate_feat_bwd = !pp.fb_table;
+  return f;
+}
+
+// The instantiated forms, X(WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW): bnf_api.hip expands the same list into its
+// launchers, so an index into kPanelForms is an index into them.  A new form is a new row here.
+#define BNF_PANEL_FORMS_H0L8(X, RT, CH, DEEP)                                                                 \
+  X(8, RT, true, DEEP, CH, 64, true, false, true) X(8, RT, true, DEEP, CH, 64, false, false, true)             \
+  X(8, RT, true, DEEP, CH, 64, true, true, false) X(8, RT, true, DEEP, CH, 64, true, false, false)             \
+  X(8, RT, true, DEEP, CH, 64, false, false, false)
+#define BNF_PANEL_FORMS_H0L4(X, FP, DEEP)                                                                     \
+  X(4, 2, true, DEEP, 1, FP, true, true, false) X(4, 2, true, DEEP, 1, FP, true, false, false)                 \
+  X(4, 2, true, DEEP, 1, FP, false, false, false)
+#define BNF_PANEL_FORMS_PLAIN(X, WN, RT, CH)                                                                  \
+  X(WN, RT, false, false, CH, 64, false, false, false) X(WN, RT, false, true, CH, 64, false, false, false)
+#define BNF_PANEL_FORMS(X)                                                                                    \
+  BNF_PANEL_FORMS_H0L8(X, 2, 2, false) BNF_PANEL_FORMS_H0L8(X, 2, 2, true)                                     \
+  BNF_PANEL_FORMS_H0L8(X, 4, 1, false) BNF_PANEL_FORMS_H0L8(X, 4, 1, true)                                     \
+  BNF_PANEL_FORMS_H0L4(X, 64, false) BNF_PANEL_FORMS_H0L4(X, 64, true)                                         \
+  BNF_PANEL_FORMS_H0L4(X, 128, false) BNF_PANEL_FORMS_H0L4(X, 128, true)                                       \
+  BNF_PANEL_FORMS_PLAIN(X, 8, 2, 2) BNF_PANEL_FORMS_PLAIN(X, 8, 4, 1) BNF_PANEL_FORMS_PLAIN(X, 4, 4, 1)
+#define BNF_PANEL_FORM_ROW(WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW) {WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW, 0, false},
+constexpr PanelForm kPanelForms[] = {BNF_PANEL_FORMS(BNF_PANEL_FORM_ROW)};
+constexpr int kNumPanelForms = (int)(sizeof(kPanelForms) / sizeof(kPanelForms[0]));
+#undef BNF_PANEL_FORM_ROW
+// the row of kPanelForms with f's nine template arguments; -1: not instantiated
+constexpr int panel_form_index(const PanelForm& f) {
+  for (int i = 0; i < kNumPanelForms; ++i) {
+    const PanelForm& r = kPanelForms[i];
+    if (r.WN == f.WN && r.RT == f.RT && r.H0L == f.H0L && r.DEEP == f.DEEP && r.CH == f.CH && r.FP == f.FP &&
+        r.F0 == f.F0 && r.C8 == f.C8 && r.FBW == f.FBW)
+      return i;
+  }
+  return -1;
+}
+
+// Every form the plans can ask for has a row, over ALL combinations of what they guarantee: h0l at W >= 512 only with
+// Fp = 64; fold0 only with h0l; c8 only with fold0; featbwd_in_wgrad only with h0l, W >= 512 and without fp8
+constexpr bool every_panel_form_has_a_row() {
+  for (int W = 256; W <= 1024; W *= 2)
+    for (int Fp = 64; Fp <= 128; Fp += 64)
+      for (int bits = 0; bits < 32; ++bits) {
+        PipelinePlan pp{};
+        StepPlan sp{};
+        pp.panel = true; pp.h0l = bits & 1; pp.fold0 = bits & 2; pp.c8 = bits & 4; sp.featbwd_in_wgrad = bits & 8;
+        if ((pp.h0l && W >= 512 && Fp != 64) || (pp.fold0 && !pp.h0l) || (pp.c8 && !pp.fold0)) continue;
+        if (sp.featbwd_in_wgrad && (!pp.h0l || W < 512 || pp.c8)) continue;
+        if (panel_form_index(make_panel_form(pp, sp, bits & 16 ? 3 : 2, W, Fp)) < 0) return false;
+      }
+  return true;
+}
+static_assert(every_panel_form_has_a_row(), "a plan can produce a panel form that BNF_PANEL_FORMS does not list");
 
 }  // namespace bnf

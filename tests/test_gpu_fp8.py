@@ -156,7 +156,8 @@ def test_fp8_vi_step_against_the_bf16_panel_step(width, depth, S, monkeypatch):
     assert not bad, (('mu', 'rho')[k], bad)   # (d bias0 = 1^T dZq_0: e5m2 alone, no averaging partner -- as in the MAP test)
 
 
-@pytest.mark.parametrize('case', ['C2-shaped', 'C5-shaped', 'W256-F49', 'NB', 'VI', 'depth3-W256', 'depth4-W512', 'W1024', 'VI-depth4'])
+@pytest.mark.parametrize('case', ['C2-shaped', 'C5-shaped', 'W256-F49', 'NB', 'VI', 'depth3-W256', 'depth4-W512', 'W1024', 'VI-depth4',
+                                  'C5-depth3'])
 def test_fp8_forward_and_backward_data_contractions_on_the_fp8_mfma(case, monkeypatch):
   """Round 6 (BASELINE configs[4] "fp8 MFMA dense layers"): on the folded row-panel forms (any depth >= 2,
   W = 256 / 512 / 1024) every W x W forward and backward-data contraction runs on v_mfma_scale_f32_32x32x64_f8f6f4 -- H_l
@@ -188,6 +189,8 @@ def test_fp8_forward_and_backward_data_contractions_on_the_fp8_mfma(case, monkey
     kw = dict(n_rows=300, width=1024, depth=2)
   elif case == 'VI-depth4':
     kw, mode, S = dict(n_rows=200, width=512, depth=4), 'vi', 2
+  elif case == 'C5-depth3':        # k_panel_fwd_bwd<4, 2, true, true, 1, 128, true, true>: the one fp8 form no other test launches
+    kw = dict(n_rows=300, width=256, depth=3, periods=(7.0, 30.4375, 365.25), harmonics=(3, 10, 10), T=2000, interactions=())
   net, model, X, y = util.make_problem(**kw)
   E = 2
   theta = util.random_theta(model, E, scale=0.3)

@@ -231,18 +231,38 @@ def test_weight_gradient_stream_kernels_match_the_two_stage_kernel(n_rows, monke
   assert not bad, bad
 
 
-@pytest.mark.parametrize('width,depth,n_rows,obs', [(512, 3, 300, 'NORMAL'), (512, 4, 1000, 'NORMAL'), (256, 4, 700, 'NORMAL'),
-                                                    (256, 3, 300, 'NB'), (512, 5, 260, 'ZINB'),
-                                                    # width 1024: 64-row panels, two 64-column slabs per wave (C4's shape class)
-                                                    (1024, 2, 300, 'NORMAL'), (1024, 4, 700, 'NORMAL'), (1024, 3, 200, 'ZINB')])
-def test_deep_panel_step_vs_oracle_and_layer_pipeline(width, depth, n_rows, obs):
+DEEP_CASES = [(512, 3, 300, 'NORMAL'), (512, 4, 1000, 'NORMAL'), (256, 4, 700, 'NORMAL'),
+              (256, 3, 300, 'NB'), (512, 5, 260, 'ZINB'),
+              # width 1024: 64-row panels, two 64-column slabs per wave (C4's shape class)
+              (1024, 2, 300, 'NORMAL'), (1024, 4, 700, 'NORMAL'), (1024, 3, 200, 'ZINB')]
+# The forms of k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW> (kPanelForms of bnf_plan.h) that no other test of the
+# suite launches (profiles/pipeline_plan_refactor.md lists which test reaches which form), each selected by its switches:
+# 2 members, 300 rows -> 512 padded rows, two to eight panels of which the last is partly padding.  (The one fp8 form
+# among them is a case of tests/test_gpu_fp8.py: the layer pipeline has no fp8 arithmetic to compare with.)
+FOLD0_OFF, WGRAD_OFF, NO_H0L = {'BNF_PANEL_FOLD0': '0'}, {'BNF_FEATBWD_WGRAD': '0'}, {'BNF_PANEL_NO_H0L': '1'}
+FP128 = dict(periods=(52.1775, 365.25), harmonics=(20, 20))      # 105 features
+FORM_CASES = [
+    ('8,2,1,0,2,64,0,0,1', 1024, 2, FOLD0_OFF, {}), ('8,2,1,0,2,64,0,0,0', 1024, 2, {**FOLD0_OFF, **WGRAD_OFF}, {}),
+    ('8,2,1,1,2,64,0,0,1', 1024, 3, FOLD0_OFF, {}), ('8,2,1,1,2,64,1,0,0', 1024, 3, WGRAD_OFF, {}),
+    ('8,2,1,1,2,64,0,0,0', 1024, 3, {**FOLD0_OFF, **WGRAD_OFF}, {}), ('8,4,1,1,1,64,0,0,0', 512, 3, {**FOLD0_OFF, **WGRAD_OFF}, {}),
+    ('4,2,1,1,1,64,0,0,0', 256, 3, FOLD0_OFF, {}), ('4,2,1,0,1,128,0,0,0', 256, 2, FOLD0_OFF, FP128),
+    ('4,2,1,1,1,128,0,0,0', 256, 3, FOLD0_OFF, FP128),
+    ('8,2,0,0,2,64,0,0,0', 1024, 2, NO_H0L, {}), ('8,4,0,0,1,64,0,0,0', 512, 2, NO_H0L, {}), ('8,4,0,1,1,64,0,0,0', 512, 3, NO_H0L, {}),
+]
+
+
+@pytest.mark.parametrize('width,depth,n_rows,obs,E,env,problem',
+                         [c + (3, {}, {}) for c in DEEP_CASES] + [(w, d, 300, 'NORMAL', 2, env, kw) for _, w, d, env, kw in FORM_CASES],
+                         ids=['-'.join(str(v) for v in c) for c in DEEP_CASES] + ['form-' + f for f, *_ in FORM_CASES])
+def test_deep_panel_step_vs_oracle_and_layer_pipeline(width, depth, n_rows, obs, E, env, problem, monkeypatch):
   """Depth > 2 through the row-panel kernel (round 3: the middle layers' contractions run out of the same LDS
   panel, their pre-activations are parked in HBM in the owning wave's register order and read back by the same
   lanes in the backward pass -- bnf_panel.h) against the float64 oracle and against the bf16 layer pipeline:
   loss, every gradient leaf, the activations H_{l+1} and dZ_l of EVERY layer as the weight-gradient kernels
-  read them, the network output."""
-  net, model, X, y = util.make_problem(n_rows=n_rows, width=width, depth=depth, observation_model=obs)
-  E = 3
+  read them, the network output.  The `form-` cases: the same comparison for the kernel forms only switches select."""
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)      # (read at bnf_create; the layer pipeline has none of these switches)
+  net, model, X, y = util.make_problem(n_rows=n_rows, width=width, depth=depth, observation_model=obs, **problem)
   theta = util.random_theta(model, E, scale=0.3)
   res, acts = {}, {}
   for pipe in ('panel', 'layers'):
