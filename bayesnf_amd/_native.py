@@ -73,7 +73,7 @@ EXPORTS = (
     'bnf_predictive_group_extremes', 'bnf_sample_pair_moments', 'bnf_predictive_group_episodes',
     'bnf_sample_ranks', 'bnf_rank_probabilities', 'bnf_predictive_group_cumulative', 'bnf_predictive_group_windows',
     'bnf_predictive_combinations', 'bnf_sample_depths', 'bnf_depth_levels', 'bnf_sample_envelope',
-    'bnf_debug_loss_and_grad',
+    'bnf_validation_check', 'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
     'bnf_kernel_flops', 'bnf_comm_available', 'bnf_comm_unique_id', 'bnf_comm_create', 'bnf_allgather',
@@ -188,6 +188,7 @@ def load():
   lib.bnf_sample_envelope.argtypes = [vp, vp, i64, i64, vp, vp, i32, i64, vp, vp]
   lib.bnf_member_log_density.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_stacking_weights.argtypes = [vp, vp, i64, i64, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
+  lib.bnf_validation_check.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp]
   lib.bnf_predictive_samples_weighted.argtypes = [vp, vp, vp, i64, i64, i64, C.c_uint64, i64, i64, vp, vp]
   lib.bnf_predictive_group_sums_weighted.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, vp, vp,
                                                      C.c_size_t, vp]

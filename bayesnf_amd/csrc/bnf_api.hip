@@ -46,6 +46,7 @@
 #include "bnf_ranking.h"
 #include "bnf_bands.h"
 #include "bnf_stacking.h"
+#include "bnf_validation.h"
 #include "bnf_plan.h"
 
 using namespace bnf;
@@ -2230,6 +2231,32 @@ int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members,
   if (lpd)
     hipLaunchKernelGGL((k_stack_rows<true>), dim3((unsigned)nt), dim3(256), 0, h->stream, logdens, M, n_rows,
                        (const double*)weights, (const double*)state, (double*)nullptr, (double*)nullptr, lpd);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- held-out validation during a fit (bnf_validation.h) ----------------------------
+int bnf_validation_check(bnf_handle* h, const double* member_ll, int64_t n_scored, int64_t epoch, int32_t check,
+                         int32_t n_checks, double* curve, double* best_score, int64_t* best_epoch, int32_t* keep,
+                         float* best_params) {
+  if (const int rc = no_device()) return rc;
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (h->cfg.forward_only || !h->params) return fail(BNF_ERR_STATE, "bnf_validation_check needs a training handle: this one is forward_only");
+  if (h->cfg.mode != BNF_MODE_MAP) return fail(BNF_ERR_STATE, "bnf_validation_check needs a MAP / MLE handle");
+  if (!member_ll || !curve || !best_score || !best_epoch || !keep || !best_params) return fail(BNF_ERR_INVALID, "argument");
+  if (n_scored < 1 || n_checks < 1 || check < 0 || check >= n_checks)
+    return fail(BNF_ERR_INVALID, "n_scored = %lld, check = %d of %d: n_scored and n_checks must be >= 1, check in [0, n_checks)",
+                (long long)n_scored, (int)check, (int)n_checks);
+  const int32_t M = h->cfg.members;
+  const size_t row_bytes = (size_t)M * (size_t)h->P * sizeof(float);
+  const char* a = (const char*)h->params;
+  const char* b = (const char*)best_params;
+  if (a < b + row_bytes && b < a + row_bytes) return fail(BNF_ERR_INVALID, "best_params overlaps the handle's parameters");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_validation_decide, dim3(cdiv(M, 256)), dim3(256), 0, h->stream, member_ll, n_scored, epoch, check,
+                     n_checks, M, curve, best_score, best_epoch, keep);
+  hipLaunchKernelGGL(k_validation_copy, dim3(cdiv(h->P, kValCopyTile), (unsigned)std::min<int32_t>(M, 65535)), dim3(256), 0,
+                     h->stream, (const uint32_t*)h->params, (int64_t)h->P, M, (const int32_t*)keep, (uint32_t*)best_params);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -198,6 +198,25 @@ class Engine:
                                        _ptr(losses)), 'bnf_train')
     return losses
 
+  def validation_check(self, member_ll, n_scored, epoch, check, n_checks, curve, best_score, best_epoch, keep,
+                       best_params):
+    """One held-out check of a MAP / MLE fit (include/bnf.h bnf_validation_check), enqueued on the handle's stream
+    without waiting: member_ll (members,) f64 as `predictive_scores` writes it for the held-out rows, n_scored of which
+    have a finite target; column `check` of curve (members, n_checks) f64 receives member_ll / n_scored, and where that
+    is the member's best so far (check 0: always) keep (members,) int32 is 1, best_score (members,) f64 and best_epoch
+    (members,) int64 are updated and the member's row of the training parameters is copied to best_params (members, P)
+    f32.  All device tensors, owned by the caller."""
+    E = self.members
+    for name, t, dtype, shape in (('member_ll', member_ll, torch.float64, (E,)), ('curve', curve, torch.float64, (E, int(n_checks))),
+                                  ('best_score', best_score, torch.float64, (E,)), ('best_epoch', best_epoch, torch.int64, (E,)),
+                                  ('keep', keep, torch.int32, (E,)), ('best_params', best_params, torch.float32, (E, self.net.P))):
+      if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device):
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}; got '
+                         f'{t.dtype} {tuple(t.shape)} on {t.device}')
+    _native.check(self.lib.bnf_validation_check(
+        self.handle, _ptr(member_ll), int(n_scored), int(epoch), int(check), int(n_checks), _ptr(curve), _ptr(best_score),
+        _ptr(best_epoch), _ptr(keep), _ptr(best_params)), 'bnf_validation_check')
+
   def set_row_tables(self, tables, epoch0=0):
     """Epoch shuffles supplied by the caller (include/bnf.h bnf_row_tables): int32 (n_epochs, members,
     (N // batch) * batch) row ids for the epochs [epoch0, epoch0 + n_epochs); uploaded and kept alive
@@ -587,7 +606,7 @@ class Engine:
     return out
 
   def predictive_scores(self, loc: torch.Tensor, aux: torch.Tensor, y: torch.Tensor, crps=None, member_ll=True,
-                        lpd=True, pit=True, weights=None) -> dict:
+                        lpd=True, pit=True, weights=None, into=None) -> dict:
     """Held-out observations y (R,) scored against the ensemble (include/bnf.h bnf_predictive_scores): loc (M, R),
     aux (M, 3) as `forward` returns them -> dict of device tensors, one per output asked for:
       'member_ll' (M,) f64   sum over the rows with a finite y of each member's log density
@@ -597,7 +616,10 @@ class Engine:
     Rows whose y is NaN come back NaN and do not enter member_ll.  Deterministic: the same call gives the same bits.
     weights (M,) array or device tensor: 'lpd', 'pit' and 'crps' are those of the mixture sum_m w_m p_m
     (bnf_predictive_scores_weighted) after the members of weight 0 are dropped; 'member_ll' is per member and comes from
-    the unweighted call on all members.  None: the equal-weight call, bit for bit."""
+    the unweighted call on all members.  None: the equal-weight call, bit for bit.
+    into {'member_ll': (M,) f64, 'work': f64 of at least M * ceil(R / BNF_SCORE_ROW_TILE)}, device tensors the CALLER
+    keeps alive, with y a float32 device tensor: 'member_ll' alone is written there, nothing is allocated here and the
+    call returns without waiting for the device (the validation checks of `inference.fit_map`)."""
     loc = loc.contiguous().float()
     aux = aux.contiguous().float()
     M, R = loc.shape
@@ -605,6 +627,16 @@ class Engine:
          ).to(self.device, dtype=torch.float32).contiguous()
     if y.shape != (R,):
       raise ValueError(f'y must hold one observation per row ({R},); got {tuple(y.shape)}')
+    if into is not None:
+      ll, work = into['member_ll'], into['work']
+      n_work = M * (-(-R // _native.SCORE_ROW_TILE))
+      if (weights is not None or ll.dtype != torch.float64 or tuple(ll.shape) != (M,) or work.dtype != torch.float64
+          or work.numel() < n_work or not ll.is_contiguous() or not work.is_contiguous()):
+        raise ValueError(f'into: member_ll (M,) f64 and work f64 of >= {n_work} are needed, and no weights')
+      _native.check(self.lib.bnf_predictive_scores(
+          self.handle, _ptr(loc), _ptr(aux), M, R, _ptr(y), _ptr(work), C.c_size_t(work.numel() * 8), _ptr(ll),
+          None, None, None), 'bnf_predictive_scores')
+      return {'member_ll': ll}
     if crps is None:
       crps = self.net.observation_model == 'NORMAL'
     if weights is not None:

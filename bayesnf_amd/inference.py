@@ -52,9 +52,67 @@ def _flatten_struct(net: NetSpec, params) -> np.ndarray:
 # ---------------------------------------------------------------------------
 # MAP / MLE
 # ---------------------------------------------------------------------------
+def validation_epochs(num_epochs, every):
+  """The epochs after which a validated fit checks the held-out rows: every, 2 every, ... and always the last one."""
+  return sorted(set(range(every, num_epochs + 1, every)) | {num_epochs})
+
+
+class _HeldOut:
+  """One shard's held-out checks during `fit_map` (include/bnf.h bnf_validation_check).  Owns a forward-only engine on
+  the training engine's device and stream -- the training handle itself cannot serve: `bnf_forward` refuses row-panel
+  handles, and on a layer pipeline its weight packing would overwrite the packed weights of the training step -- the
+  device copies of the held-out rows, and the buffers of the checks: the curve, every member's best score and epoch and
+  the snapshot of its parameters at that epoch.  The forward reads theta straight from the training engine's `params`
+  tensor (no copy); everything is enqueued, nothing is waited for."""
+
+  def __init__(self, net, eng, features_val, target_val, epochs, compute_dtype, device_index):
+    self.eng, self.epochs, self.done = eng, list(epochs), 0
+    E, n_val = eng.members, features_val.shape[0]
+    # capacity: the rule of _forward_local
+    cells = max(1, (1 << 28) // max(1, net.width))
+    row_cap = int(min(n_val, _ROW_CHUNK))
+    mem_cap = int(max(1, min(E, cells // row_cap)))
+    self.fwd = Engine(net, mode='map', members=mem_cap, forward_only=True, row_capacity=row_cap,
+                      compute_dtype=compute_dtype, device_index=device_index)
+    dev = eng.device
+    self.X = torch.from_numpy(np.ascontiguousarray(features_val, dtype=np.float32)).to(dev)
+    self.y = torch.from_numpy(np.ascontiguousarray(target_val, dtype=np.float32)).to(dev)
+    self.n = int(np.isfinite(target_val).sum())
+    self.theta = eng.params.view(E, net.P)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    self.curve, self.best_score, self.ll = f64(E, len(self.epochs)), f64(E), f64(E)
+    self.work = f64(max(1, E * (-(-n_val // _native.SCORE_ROW_TILE))))
+    self.best_epoch = torch.empty((E,), dtype=torch.int64, device=dev)
+    self.keep = torch.empty((E,), dtype=torch.int32, device=dev)
+    self.best_params = torch.empty((E, net.P), dtype=torch.float32, device=dev)
+
+  def check(self, epoch):
+    loc, aux = self.fwd.forward(self.theta, self.X)
+    self.fwd.predictive_scores(loc, aux, self.y, crps=False, member_ll=True, lpd=False, pit=False,
+                               into={'member_ll': self.ll, 'work': self.work})
+    self.eng.validation_check(self.ll, self.n, epoch, self.done, len(self.epochs), self.curve, self.best_score,
+                              self.best_epoch, self.keep, self.best_params)
+    self.done += 1
+
+  def train(self, e0, n):
+    """The epochs [e0, e0 + n) in segments cut at the check epochs, each check right after its epoch -> loss pieces."""
+    parts, stop = [], e0 + n
+    while e0 < stop:
+      nxt = self.epochs[self.done] if self.done < len(self.epochs) else stop
+      e1 = min(stop, nxt)
+      parts.append(self.eng.train(e0, e1 - e0))
+      if e1 == nxt:
+        self.check(e1)
+      e0 = e1
+    return parts
+
+  def close(self):
+    self.fwd.close()
+
+
 def fit_map(features, target, seed, observation_model, model_args, num_particles,
             learning_rate, num_epochs, prior_weight=1.0, batch_size=None,
-            num_splits=1, compute_dtype=None, init_rng=None):
+            num_splits=1, compute_dtype=None, init_rng=None, validation=None):
   """Fit `num_particles` MAP (or MLE, prior_weight=0) members.
 
   init_rng: 'jax' (default; env BNF_INIT_RNG) starts every member from the initial parameters the
@@ -69,11 +127,35 @@ def fit_map(features, target, seed, observation_model, model_args, num_particles
   Returns (params, losses): params is a StructTuple whose leaves have shape
   (num_devices, num_particles // num_devices, *leaf_shape); losses has shape
   (num_devices, num_particles // num_devices, num_epochs).
+
+  validation = (features_val, target_val, every, restore_best): held-out rows (NaN targets allowed: left out) scored
+  after the epochs `validation_epochs(num_epochs, every)` -- training runs in segments between the checks, every shard
+  validates its own members on its own device with a forward-only engine, nothing is waited for (`_HeldOut`, include/bnf.h
+  bnf_validation_check) -- and a third value is returned, a dict:
+    'epochs' (K,) int                    'member_log_density' lead dims of losses[..., 0] + (K,) float64: every member's
+    'best', 'best_epoch' lead dims       mean held-out log density at each check; its maximum (first occurrence; a NaN
+    'n' rows scored  'restored' bool     never beats a number) and the epoch of that check
+  With restore_best the returned params are every member's own at its 'best_epoch', else the final ones; losses are the
+  same either way.  None: the Engine calls, and the two return values, of a fit without validation.
   """
   net = _net_from_args(model_args, observation_model)
   features = np.asarray(features, dtype=np.float64)
   target = np.asarray(target, dtype=np.float64)
   n_rows = target.shape[0]
+  checks = None
+  if validation is not None:
+    features_val, target_val, every, restore_best = validation
+    features_val = np.asarray(features_val, dtype=np.float64)
+    target_val = np.asarray(target_val, dtype=np.float64)
+    every = int(every)
+    if features_val.ndim != 2 or features_val.shape[1] != features.shape[1] or target_val.shape != (features_val.shape[0],):
+      raise ValueError(f'validation: features ({features_val.shape}) need the columns of the training features and one '
+                       f'target per row; got targets {target_val.shape}')
+    if not np.isfinite(target_val).any():
+      raise ValueError('validation: no row with a finite target')
+    if every < 1 or num_epochs < 1:
+      raise ValueError(f'validation: every={every} and num_epochs={num_epochs} must be >= 1')
+    checks = validation_epochs(num_epochs, every)
   if batch_size is None:
     batch_size = n_rows
   world = distributed.device_count()
@@ -85,7 +167,7 @@ def fit_map(features, target, seed, observation_model, model_args, num_particles
   init_rng = init_rng or os.environ.get('BNF_INIT_RNG', 'jax')
   if init_rng not in ('jax', 'philox'):
     raise ValueError("init_rng must be 'jax' or 'philox'")
-  thetas, losses = [], []
+  thetas, losses, curves, bests, best_epochs = [], [], [], [], []
   for i in range(num_splits):
     seed_i = _native.fold_in(seed64, i) if num_splits > 1 else seed64
     keys = (jaxseed.member_keys(seed, world, per_device, i if num_splits > 1 else None)
@@ -116,30 +198,50 @@ def fit_map(features, target, seed, observation_model, model_args, num_particles
         eng.init_params_keys(jaxseed.map_leaf_keys(net, keys[sh.index]), log_noise_init)
       else:
         eng.init_params(log_noise_init)
+      # held-out checks: the epochs run in segments cut at the check epochs, each check enqueued right after its epoch
+      held = (None if checks is None else
+              _HeldOut(net, eng, features_val, target_val, checks, compute_dtype, sh.device))
+      train = (lambda e0, n: [eng.train(e0, n)]) if held is None else held.train
+      joined = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
       if pkeys is None:
-        return eng, eng.train(0, num_epochs)
+        return eng, joined(train(0, num_epochs)), held
       # the shuffles are drawn on the device, epoch by epoch, from the sub keys of their sort rounds
       # (BNF_ROW_TABLES=host: drawn here instead -- threefry bits + stable sort per member and epoch -- and uploaded
       # in chunks of <= ~64 MB of row ids, chunk c + 1 while the device runs the epochs of chunk c)
       if os.environ.get('BNF_ROW_TABLES', 'device') != 'host':
         eng.set_row_keys(jaxseed.map_shuffle_subkeys(pkeys[sh.index], n_rows), epoch0=0)
-        return eng, eng.train(0, num_epochs)
+        return eng, joined(train(0, num_epochs)), held
       keep = (n_rows // batch_size) * batch_size
       per_chunk = int(max(1, min(num_epochs, (64 << 20) // max(1, 4 * per_device * keep))))
       parts = []
       for e0 in range(0, num_epochs, per_chunk):
         n = min(per_chunk, num_epochs - e0)
         eng.set_row_tables(jaxseed.map_row_tables(pkeys[sh.index][:, e0:e0 + n], n_rows, batch_size), epoch0=e0)
-        parts.append(eng.train(e0, n))
-      return eng, torch.cat(parts, dim=1)
+        parts.extend(train(e0, n))
+      return eng, torch.cat(parts, dim=1), held
 
     runs = distributed.run_shards(train_shard)
-    thetas.append(distributed.gather_shards([e.params.view(per_device, net.P) for e, _ in runs]).cpu().numpy())
-    losses.append(distributed.gather_shards([l for _, l in runs]).cpu().numpy())
-    for e, _ in runs:
+    gathered = lambda parts: distributed.gather_shards(parts).cpu().numpy()
+    if checks is not None and restore_best:
+      thetas.append(gathered([h.best_params for _, _, h in runs]))
+    else:
+      thetas.append(gathered([e.params.view(per_device, net.P) for e, _, _ in runs]))
+    losses.append(gathered([l for _, l, _ in runs]))
+    if checks is not None:
+      curves.append(gathered([h.curve for _, _, h in runs]))
+      bests.append(gathered([h.best_score for _, _, h in runs]))
+      best_epochs.append(gathered([h.best_epoch for _, _, h in runs]))
+    for e, _, h in runs:
+      if h is not None:
+        h.close()
       e.close()
   theta = np.concatenate(thetas, axis=1)          # (world, E/world, P)
-  return _struct_tuple(net, theta), np.concatenate(losses, axis=1)
+  if checks is None:
+    return _struct_tuple(net, theta), np.concatenate(losses, axis=1)
+  info = {'epochs': np.asarray(checks, dtype=np.int64), 'member_log_density': np.concatenate(curves, axis=1),
+          'best': np.concatenate(bests, axis=1), 'best_epoch': np.concatenate(best_epochs, axis=1),
+          'n': int(np.isfinite(target_val).sum()), 'restored': bool(restore_best)}
+  return _struct_tuple(net, theta), np.concatenate(losses, axis=1), info
 
 
 # ---------------------------------------------------------------------------

@@ -35,6 +35,7 @@ Differences a caller can see:
 
 from __future__ import annotations
 
+import numbers
 import types
 from collections.abc import Sequence
 
@@ -1503,12 +1504,41 @@ class BayesianNeuralFieldMAP(BayesianNeuralFieldEstimator):
 
   _ensemble_dims = 2
 
+  validation_ = None
+
   def fit(self, table, seed, ensemble_size=16, learning_rate=0.005,
-          num_epochs=5_000, batch_size=None, num_splits=1):
+          num_epochs=5_000, batch_size=None, num_splits=1, validation=None, validation_every=None, restore_best=True):
     """Train `ensemble_size` independent members; members are sharded over the
     GPUs (ranks) of the job.  `batch_size=None` is full batch; otherwise each
     epoch does len(table)//batch_size Adam steps on a per-member shuffle.
-    `num_splits` trains the ensemble in that many sequential chunks."""
+    `num_splits` trains the ensemble in that many sequential chunks.
+
+    validation: a table of held-out rows that holds the target column, scored on the GPU while the fit runs (the target
+    checks are those of `score`: NaN targets are left out, infinite or -- count models -- non-integer targets, a missing
+    target column and a table without a finite target are a ValueError before any GPU work).  Every member's mean
+    held-out log density is recorded after the epochs validation_every, 2 validation_every, ... and after the last one;
+    validation_every counts the epochs `fit` actually runs (the columns of `losses_`) and defaults to
+    ceil(num_epochs / 50).  The decision and the snapshots stay on the device: the fit waits for nothing.  Afterwards
+    `validation_` is a dict (None after a fit without validation):
+      'epochs' (K,) int                 the epochs of the checks
+      'member_log_density'              lead dims of losses_[..., 0] + (K,) float64: mean held-out log density per
+                                        member and check
+      'best', 'best_epoch'              lead dims: each member's largest value (the first of equal ones; a NaN never
+                                        beats a number) and the epoch of that check
+      'n' rows scored                   'restored' what restore_best was
+    restore_best=True leaves every member in `params_` at its OWN best epoch, False at the last epoch; `losses_` is the
+    same either way.  Out of scope: `BayesianNeuralFieldVI.fit` (its held-out score is a mixture over posterior draws and
+    would need draws at every check); early stopping (a host sync per check and one decision across the shards); the
+    curve of the ensemble mixture (all shards' rows on one device at every check)."""
+    held = None
+    if validation is not None:
+      y_val = self._targets('fit: validation', validation)
+      if not np.isfinite(y_val).any():
+        raise ValueError('fit: validation: no row with a finite target')
+    if validation_every is not None:
+      if (isinstance(validation_every, bool) or not isinstance(validation_every, numbers.Integral)
+          or validation_every < 1):
+        raise ValueError(f'fit: validation_every must be an integer >= 1; got {validation_every!r}')
     if ensemble_size < distributed.device_count():
       raise ValueError('ensemble_size cannot be smaller than device_count. '
                        'https://github.com/google/bayesnf/issues/28.')
@@ -1518,7 +1548,11 @@ class BayesianNeuralFieldMAP(BayesianNeuralFieldEstimator):
       batch_size = x.shape[0]
     if self._scale_epochs_by_batch_size:
       num_epochs = num_epochs * (x.shape[0] // batch_size)
-    self.params_, self.losses_ = inference.fit_map(
+    if validation is not None:
+      every = max(1, -(-num_epochs // 50)) if validation_every is None else int(validation_every)
+      held = (self.data_handler.get_test(validation), y_val, every, bool(restore_best))
+    # (without validation fit_map is called exactly as before, and returns its two values)
+    fitted = inference.fit_map(
         x, y,
         seed=seed,
         observation_model=self.observation_model,
@@ -1530,7 +1564,10 @@ class BayesianNeuralFieldMAP(BayesianNeuralFieldEstimator):
         batch_size=batch_size,
         num_splits=num_splits,
         compute_dtype=self.compute_dtype,
-        init_rng=self.init_rng)
+        init_rng=self.init_rng,
+        **({} if held is None else {'validation': held}))
+    self.params_, self.losses_ = fitted[0], fitted[1]
+    self.validation_ = None if held is None else fitted[2]
     return self
 
 

@@ -641,6 +641,37 @@ int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members,
                          int64_t max_iter, double tol, void* work, size_t work_bytes, double* weights, float* lpd,
                          double* info);
 
+/* VALIDATION ON HELD-OUT ROWS DURING A FIT: one check.  Between two segments of bnf_train the caller scores the held-out
+ * rows -- bnf_forward on a forward-only handle whose theta IS the training handle's parameter buffer, then
+ * bnf_predictive_scores' member_ll -- and this call records every member's mean held-out log density and keeps a snapshot
+ * of the member's parameters where the check is its best so far.  The decision is taken and the snapshot kept on the
+ * device: a fit with checks has no more host round trips than one without.  The reference has no counterpart (its
+ * ensemble_map runs num_epochs and returns the last parameters, inference.py:577-619).
+ *   h            a bound MAP / MLE TRAINING handle: its members (cfg.members) and bound parameters (members, P) f32
+ *   member_ll    DEVICE (members,) f64 as bnf_predictive_scores writes it for the held-out rows
+ *   n_scored     the held-out rows with a finite target, >= 1 (the host knows it)
+ *   epoch        epochs completed so far, recorded with the snapshot
+ *   check, n_checks   index of this check and the number of checks of the fit: 0 <= check < n_checks
+ *   curve        DEVICE (members, n_checks) f64 row-major: column `check` is written
+ *   best_score   DEVICE (members,) f64 in/out     best_epoch DEVICE (members,) int64 in/out
+ *   keep         DEVICE (members,) int32 out: 1 where this check became the member's best, else 0
+ *   best_params  DEVICE (members, P) f32 in/out: the snapshots; must not overlap the handle's parameters
+ * SCORE: score_m = member_ll[m] / (double)n_scored, one f64 division; curve[m][check] = score_m.
+ * RULE: at check == 0, keep[m] = 1 always: whatever the score is, NaN or -inf included, it initialises best_score,
+ *   best_epoch and best_params, so none of them is ever read uninitialised.  At check > 0,
+ *   keep[m] = score_m > best_score[m] || (isnan(best_score[m]) && !isnan(score_m)): a tie keeps the earlier epoch, a NaN
+ *   never replaces a number, -inf never replaces -inf.
+ * SNAPSHOT: where keep[m] is set, best_score[m] = score_m, best_epoch[m] = epoch and row m of the handle's parameters is
+ *   copied to row m of best_params, bit for bit.  Rows with keep[m] == 0 are not touched.
+ * Two kernels (bnf_validation.h): the decision over the members, then the copy over (ceil(P / tile), members), which reads
+ *   the finished decision.  No floating-point atomics: two calls give the same bits.
+ * BNF_ERR_STATE for an unbound, a forward-only and a VI handle; BNF_ERR_INVALID for a NULL pointer, n_scored < 1,
+ *   n_checks < 1, check outside [0, n_checks) and a best_params that overlaps the parameters; nothing is launched then.
+ * Runs on the handle's stream and does not synchronise; reads the training parameters, writes none of the training state. */
+int bnf_validation_check(bnf_handle* h, const double* member_ll, int64_t n_scored, int64_t epoch, int32_t check,
+                         int32_t n_checks, double* curve, double* best_score, int64_t* best_epoch, int32_t* keep,
+                         float* best_params);
+
 /* SUMMARIES of an ensemble of sample paths, column by column: x DEVICE (n_samples, n_cols) f64 row-major -- the layout
  * bnf_predictive_group_sums writes, one column per group total -- and optionally the observed totals y DEVICE (n_cols,)
  * f64.  What a user of the totals would otherwise compute on the host from the whole matrix (np.quantile, an O(S^2) loop
