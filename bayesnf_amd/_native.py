@@ -37,6 +37,12 @@ GROUP_TILE = 1024   # BNF_GROUP_TILE: rows per partial sum of bnf_predictive_gro
 EXTREMES_WORK_PER_TILE = 32   # BNF_EXTREMES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_extremes' work buffer
 EPISODES_WORK_PER_TILE = 80   # BNF_EPISODES_WORK_PER_TILE: bytes per tile and path of bnf_predictive_group_episodes' work buffer
 STACK_ROW_TILE, STACK_STATE_DOUBLES = 1024, 8   # BNF_STACK_*: size the work buffer of bnf_stacking_weights
+SCENARIO_MAX_SAMPLES = 4096   # BNF_SCENARIO_MAX_SAMPLES: most sample paths of bnf_sample_distances / bnf_scenario_select
+
+
+def scenario_work_bytes(n_samples: int) -> int:
+  """Bytes of the work buffer of bnf_scenario_select (the formula of include/bnf.h)."""
+  return 20 * int(n_samples) + 16
 
 
 def pair_work_doubles(n_cols: int) -> int:
@@ -73,7 +79,7 @@ EXPORTS = (
     'bnf_predictive_group_extremes', 'bnf_sample_pair_moments', 'bnf_predictive_group_episodes',
     'bnf_sample_ranks', 'bnf_rank_probabilities', 'bnf_predictive_group_cumulative', 'bnf_predictive_group_windows',
     'bnf_predictive_combinations', 'bnf_sample_depths', 'bnf_depth_levels', 'bnf_sample_envelope',
-    'bnf_validation_check', 'bnf_debug_loss_and_grad',
+    'bnf_sample_distances', 'bnf_scenario_select', 'bnf_validation_check', 'bnf_debug_loss_and_grad',
     'bnf_debug_row_index', 'bnf_debug_vi_eps', 'bnf_debug_vi_noise', 'bnf_debug_activation',
     'bnf_debug_gemm_nt', 'bnf_debug_gemm_tn', 'bnf_debug_poison_lds', 'bnf_profile_enable', 'bnf_profile_read',
     'bnf_kernel_flops', 'bnf_comm_available', 'bnf_comm_unique_id', 'bnf_comm_create', 'bnf_allgather',
@@ -186,6 +192,8 @@ def load():
   lib.bnf_depth_levels.argtypes = [vp, vp, i64, i64, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, vp, vp, vp, vp,
                                    vp]
   lib.bnf_sample_envelope.argtypes = [vp, vp, i64, i64, vp, vp, i32, i64, vp, vp]
+  lib.bnf_sample_distances.argtypes = [vp, vp, i64, i64, vp, vp, i32, vp, vp]
+  lib.bnf_scenario_select.argtypes = [vp, vp, i64, i32, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
   lib.bnf_member_log_density.argtypes = [vp, vp, vp, i64, i64, vp, vp]
   lib.bnf_stacking_weights.argtypes = [vp, vp, i64, i64, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
   lib.bnf_validation_check.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp]

@@ -45,6 +45,7 @@
 #include "bnf_dependence.h"
 #include "bnf_ranking.h"
 #include "bnf_bands.h"
+#include "bnf_scenarios.h"
 #include "bnf_stacking.h"
 #include "bnf_validation.h"
 #include "bnf_plan.h"
@@ -2421,6 +2422,63 @@ int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, i
       hipLaunchKernelGGL(k_vario_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, nT * (nT + 1) / 2, y,
                          n_cols, score);
   }
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+// ---- representative scenarios: pairwise distances of the paths, forward selection (bnf_scenarios.h) ------
+static int scenario_sizes(const bnf_handle* h, int64_t n_samples) {
+  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
+  if (n_samples < 1) return fail(BNF_ERR_INVALID, "argument");
+  if (n_samples > BNF_SCENARIO_MAX_SAMPLES)
+    return fail(BNF_ERR_INVALID, "%lld sample paths: the distance matrix has at most %d a side", (long long)n_samples,
+                BNF_SCENARIO_MAX_SAMPLES);
+  return BNF_OK;
+}
+
+int bnf_sample_distances(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
+                         const double* y, int32_t p, double* dist, double* ydist) {
+  if (const int rc = no_device()) return rc;
+  if (const int rc = scenario_sizes(h, n_samples)) return rc;
+  if (!x || !dist || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
+  if (p != 1 && p != 2) return fail(BNF_ERR_INVALID, "p = %d: the distance is the 1-norm (p = 1) or the 2-norm (p = 2)", p);
+  if ((y == nullptr) != (ydist == nullptr))
+    return fail(BNF_ERR_INVALID, "y and ydist go together: both, or both NULL");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (p == 1 && scale) launch_scn_distances<1, true>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
+  else if (p == 1) launch_scn_distances<1, false>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
+  else if (scale) launch_scn_distances<2, true>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
+  else launch_scn_distances<2, false>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
+  HIPCHK(hipGetLastError());
+  return BNF_OK;
+}
+
+int bnf_scenario_select(bnf_handle* h, const double* dist, int64_t n_samples, int32_t k, const double* ydist, void* work,
+                        size_t work_bytes, int32_t* chosen, double* objective, double* prob, int32_t* assign,
+                        double* nearest, int32_t* obs_nearest, double* obs) {
+  if (const int rc = no_device()) return rc;
+  if (const int rc = scenario_sizes(h, n_samples)) return rc;
+  if (k < 1 || k > n_samples)
+    return fail(BNF_ERR_INVALID, "k = %d: 1..%lld, the number of sample paths", k, (long long)n_samples);
+  if (!dist || !chosen || !objective || !prob) return fail(BNF_ERR_INVALID, "argument");
+  if (ydist && (!obs_nearest || !obs)) return fail(BNF_ERR_INVALID, "ydist needs obs_nearest and obs");
+  const size_t need = scenario_work_bytes(n_samples);
+  if (!work || work_bytes < need || ((uintptr_t)work & 7u))
+    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld sample paths need %zu, 8-byte aligned",
+                work ? work_bytes : (size_t)0, (long long)n_samples, need);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const ScnWork w = scenario_work(work, n_samples);
+  const int64_t S = n_samples;
+  HIPCHK(hipMemsetAsync(w.flag, 0, 2 * sizeof(int32_t), h->stream));
+  hipLaunchKernelGGL(k_scn_init, dim3(std::min<unsigned>(1024u, cdiv(S * S, 256 * 4))), dim3(256), 0, h->stream, dist, S, w);
+  for (int32_t i = 0; i < k; ++i) {
+    hipLaunchKernelGGL(k_scn_sums, dim3((unsigned)S), dim3(kScnThreads), 0, h->stream, dist, S, w);
+    hipLaunchKernelGGL(k_scn_pick, dim3(1), dim3(kScnThreads), 0, h->stream, dist, S, i, w, chosen, objective);
+  }
+  hipLaunchKernelGGL(k_scn_assign, dim3(cdiv(S, 256)), dim3(256), 0, h->stream, dist, S, k, w, (const int32_t*)chosen,
+                     assign, nearest);
+  hipLaunchKernelGGL(k_scn_finish, dim3((unsigned)k + 1u), dim3(kScnThreads), 0, h->stream, S, k, w,
+                     (const int32_t*)chosen, ydist, prob, obs_nearest, obs);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }

@@ -843,6 +843,69 @@ class Engine:
       out['variogram_score'] = float(score.cpu()[0])
     return out
 
+  def sample_distances(self, x, p, scale=None, y=None):
+    """The pairwise distances of the joint paths x (S, C) f64 (include/bnf.h bnf_sample_distances) -> (dist, ydist):
+    dist (S, S) f64 device tensor, dist[s][t] = sum_c |x_sc - x_tc| (p = 1) or sqrt(sum_c (x_sc - x_tc)^2) (p = 2), with
+    scale (C,) every difference divided by scale_c; ydist (S,) the same distance between every path and y (C,), None
+    without y.  With y only the columns whose y_c is finite take part.  The matrix is whole and bitwise symmetric, the
+    diagonal +0.0; a path with a NaN is NaN in its row and column.  A cell's bits depend on its two paths and the
+    participating columns only.  S > BNF_SCENARIO_MAX_SAMPLES or another p is a ValueError.  S^2 C / 2 differences.
+    Deterministic."""
+    x = self._as_f64(x, None, 'x')
+    if x.dim() != 2:
+      raise ValueError(f'x must be (n_samples, n_cols); got {tuple(x.shape)}')
+    S, G = x.shape
+    if S < 1 or G < 1:
+      raise ValueError(f'x must hold at least one path and one column; got {tuple(x.shape)}')
+    if S > _native.SCENARIO_MAX_SAMPLES:
+      raise ValueError(f'{S} sample paths: the distance matrix has at most {_native.SCENARIO_MAX_SAMPLES} a side')
+    scale = None if scale is None else self._as_f64(scale, (G,), 'scale')
+    y = None if y is None else self._as_f64(y, (G,), 'y')
+    dist = torch.empty((S, S), dtype=torch.float64, device=self.device)
+    ydist = None if y is None else torch.empty((S,), dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_sample_distances(self.handle, _ptr(x), S, G, _ptr(scale), _ptr(y), int(p), _ptr(dist),
+                                                _ptr(ydist)), 'bnf_sample_distances')
+    torch.cuda.synchronize(self.device)     # device copies of `x`, `scale` and `y` made here are released on return
+    return dist, ydist
+
+  def scenario_select(self, dist, k, ydist=None) -> dict:
+    """Fast forward selection of k scenarios on the symmetric distance matrix dist (S, S) f64 `sample_distances` returns
+    (include/bnf.h bnf_scenario_select) -> dict of device tensors:
+      'chosen' (k,) int32       the paths picked, in the order picked: each minimises sum_s min(nearest so far, dist[s][u]),
+                                the lowest index among equal ones
+      'objective' (k,) f64      that sum / S after 1 .. k scenarios: the Kantorovich distance to the ensemble, nonincreasing
+      'prob' (k,) f64           the share of the paths nearest to each scenario (the earliest chosen among equally near)
+      'assign' (S,) int32       the scenario 0 .. k - 1 of every path        'nearest' (S,) f64   its distance to it
+    and with ydist (S,), the distances of an observed vector:
+      'obs_nearest' (1,) int32  the scenario nearest to the observed vector
+      'obs' (3,) f64            that distance, and the shares of the paths whose 'nearest' is <= and < it
+    A NaN cell in dist gives -1 / NaN everywhere.  1 <= k <= S <= BNF_SCENARIO_MAX_SAMPLES, ValueError otherwise.  k S^2
+    reads of dist, all steps enqueued at once.  Deterministic."""
+    if not (isinstance(dist, torch.Tensor) and dist.dim() == 2 and dist.shape[0] == dist.shape[1]
+            and dist.dtype == torch.float64):
+      raise ValueError('dist must be the (n_samples, n_samples) f64 device tensor sample_distances returns')
+    dist = dist.to(self.device).contiguous()
+    S = dist.shape[0]
+    k = int(k)
+    if S < 1 or S > _native.SCENARIO_MAX_SAMPLES:
+      raise ValueError(f'{S} sample paths: 1..{_native.SCENARIO_MAX_SAMPLES}')
+    if not 1 <= k <= S:
+      raise ValueError(f'k={k}: 1..{S}, the number of sample paths')
+    ydist = None if ydist is None else self._as_f64(ydist, (S,), 'ydist')
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=self.device)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+    out = {'chosen': i32(k), 'objective': f64(k), 'prob': f64(k), 'assign': i32(S), 'nearest': f64(S)}
+    if ydist is not None:
+      out['obs_nearest'], out['obs'] = i32(1), f64(3)
+    n_work = _native.scenario_work_bytes(S)
+    work = torch.empty(-(-n_work // 8), dtype=torch.float64, device=self.device)
+    _native.check(self.lib.bnf_scenario_select(
+        self.handle, _ptr(dist), S, k, _ptr(ydist), _ptr(work), C.c_size_t(n_work), _ptr(out['chosen']),
+        _ptr(out['objective']), _ptr(out['prob']), _ptr(out['assign']), _ptr(out['nearest']), _ptr(out.get('obs_nearest')),
+        _ptr(out.get('obs'))), 'bnf_scenario_select')
+    torch.cuda.synchronize(self.device)     # `work` and the device copies made here are released on return
+    return out
+
   def sample_ranks(self, x, scale=None) -> dict:
     """How the columns of every joint path of x (S, G) f64 rank against each other (include/bnf.h bnf_sample_ranks), on
     the values x / scale with scale (G,) an optional per-column divisor -> dict of (S, G) device tensors:

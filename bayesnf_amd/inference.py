@@ -792,6 +792,74 @@ def dependence_summaries(features, observation_model, params, model_args, num_sa
     return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in res.items()}
 
 
+SCENARIO_NORMS = (1, 2)      # the norms the path distances are compiled for (include/bnf.h bnf_sample_distances)
+
+
+def scenario_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups, k,
+                       norm=2, scale=None, observed=None, compute_dtype=None, weights=None):
+  """The joint sample paths reduced to k representative scenarios on the GPU -- fast forward selection (Heitsch & Roemisch
+  2003): the (num_samples, G) matrix of group totals `sample_predictive(..., groups=groups)` would return stays on the
+  device (include/bnf.h bnf_predictive_group_sums), the paths' pairwise distances are formed there (bnf_sample_distances:
+  the `norm`-norm, 1 or 2, of the difference of two vectors of totals, every total divided by scale (G,) finite and > 0 when
+  given), the scenarios are picked there (bnf_scenario_select) and their k rows of totals gathered there.  groups =
+  (seg_offsets, seg_rows) as `csr_from_codes` builds them; observed (G,) the observed totals, NaN where a group is to be
+  left out of every distance.  -> dict of numpy arrays:
+    'scenarios' (k, G) f64      the totals of the chosen paths, in the order chosen
+    'path' (k,) int64           their indices among the sample paths
+    'probability' (k,) f64      the share of the paths nearest to each (the earliest chosen among equally near)
+    'distance' (k,) f64         the Kantorovich distance between the ensemble and the first 1 .. k scenarios, nonincreasing
+    'assignment' (num_samples,) int64   the scenario of every path
+  and with `observed`:
+    'nearest' int               the scenario nearest to the observed vector      'nearest_distance' float
+    'pit' (2,) f64              the shares of the paths whose distance to their scenario is <= and < 'nearest_distance'
+  1 <= k <= num_samples <= 4,096 (BNF_SCENARIO_MAX_SAMPLES: the distance matrix is held whole), ValueError beyond, before
+  any GPU work.  num_samples^2 G / 2 differences, k num_samples^2 reads of the matrix.
+  weights: member weights of the sample paths as in `sample_predictive`; None: equal weights."""
+  num_samples = _num_samples(num_samples)
+  if num_samples > _native.SCENARIO_MAX_SAMPLES:
+    raise ValueError(f'num_samples={num_samples}: the scenarios are chosen among at most {_native.SCENARIO_MAX_SAMPLES} '
+                     'sample paths')
+  if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= num_samples:
+    raise ValueError(f'k={k!r}: an integer in 1..{num_samples}, the number of sample paths')
+  k = int(k)
+  if isinstance(norm, bool) or norm not in SCENARIO_NORMS:
+    raise ValueError(f'norm={norm!r}: the distance between two paths is formed for norm in {SCENARIO_NORMS}')
+  norm = int(norm)
+  seg_offsets, seg_rows = groups
+  n_groups = len(seg_offsets) - 1
+  _check_cells(num_samples, n_groups)
+  if scale is not None:
+    try:
+      scale = np.ascontiguousarray(scale, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'scale must be an array of numbers of shape ({n_groups},)') from e
+    if scale.shape != (n_groups,):
+      raise ValueError(f'scale must hold one divisor per group ({n_groups},); got {scale.shape}')
+    if not (np.all(np.isfinite(scale)) and np.all(scale > 0)):
+      raise ValueError('scale must be finite and > 0')
+  observed = _per_group('observed', 'total', observed, n_groups)
+  if observed is not None and not np.isfinite(observed).any():
+    raise ValueError('observed: no group has an observed total')
+  with _sample_paths(features, observation_model, params, model_args, ensemble_dims, compute_dtype, weights,
+                     seed) as (eng, loc, aux, seed64, kw):
+    totals = eng.predictive_group_sums(loc, aux, seg_offsets, seg_rows, num_samples, seed64, **kw)
+    sc = None if scale is None else torch.from_numpy(scale).to(eng.device)
+    y = None if observed is None else torch.from_numpy(observed).to(eng.device)
+    dist, ydist = eng.sample_distances(totals, norm, sc, y)
+    res = eng.scenario_select(dist, k, ydist)
+    scenarios = totals.index_select(0, res['chosen'].clamp(min=0).to(torch.int64))       # (-1: a NaN total; NaN below)
+    host = lambda t: t.cpu().numpy()
+    path = host(res['chosen']).astype(np.int64)
+    out = {'scenarios': host(scenarios), 'path': path, 'probability': host(res['prob']),
+           'distance': host(res['objective']), 'assignment': host(res['assign']).astype(np.int64)}
+    if np.any(path < 0):
+      out['scenarios'][:] = np.nan
+    if y is not None:
+      obs = host(res['obs'])
+      out.update(nearest=int(host(res['obs_nearest'])[0]), nearest_distance=float(obs[0]), pit=obs[1:3].copy())
+    return out
+
+
 def ranking_summaries(features, observation_model, params, model_args, num_samples, seed, ensemble_dims, groups,
                       observed=None, scale=None, top_k=1, quantiles=(), compute_dtype=None, weights=None):
   """How the group totals of the joint sample paths rank against each other within a path, formed and scored on the GPU:

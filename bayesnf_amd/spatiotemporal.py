@@ -733,8 +733,8 @@ class BayesianNeuralFieldEstimator:
       'n', 'dropped'                  rows scored; rows to which every member with a positive weight gives density 0
     The weights are taken by `predict_samples`, `predict_totals`, `score_totals`, `predict_extremes`, `score_extremes`,
     `predict_episodes`, `score_episodes`, `predict_cumulative`, `score_cumulative`, `predict_windows`, `score_windows`,
-    `predict_dependence`, `score_dependence`, `predict_ranking`, `score_ranking`, `predict_combinations` and
-    `score_combinations`
+    `predict_dependence`, `score_dependence`, `predict_ranking`, `score_ranking`, `predict_scenarios`, `score_scenarios`,
+    `predict_combinations` and `score_combinations`
     (weights=...) and scored on another table by `weighted_log_density`; they are taken by the marginal forecast as well:
     `predict` and `score` (weights=...) give the quantiles, log density, pit, crps and rps of the weighted mixture.
     `fit` is unchanged."""
@@ -1389,6 +1389,79 @@ class BayesianNeuralFieldEstimator:
       w = np.asarray(pair_weights, dtype=np.float64)[np.ix_(scored, scored)]
       total = float(np.sum(np.triu(w, 1), dtype=np.float64))
     res['mean_variogram_score'] = res['variogram_score'] / total if res['n_pairs'] > 0 and total > 0 else float('nan')
+    return res
+
+  def _scenario_summaries(self, what, table, group_by, k, norm, scale, num_samples, seed, weights, target=False):
+    f = self._paths(what, table, group_by, num_samples, seed, weights, target=target)
+    cap = inference._native.SCENARIO_MAX_SAMPLES
+    if int(num_samples) > cap:
+      raise ValueError(f'{what}: num_samples={num_samples}: the scenarios are chosen among at most {cap} sample paths')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= int(num_samples):
+      raise ValueError(f'{what}: k={k!r}: an integer in 1..{int(num_samples)}, the number of sample paths')
+    if isinstance(norm, bool) or norm not in inference.SCENARIO_NORMS:
+      raise ValueError(f'{what}: norm={norm!r}: the distance between two paths is formed for norm in '
+                       f'{inference.SCENARIO_NORMS}')
+    n_groups = len(f.keys)
+    if scale is not None:
+      try:
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+      except (TypeError, ValueError) as e:
+        raise ValueError(f'{what}: scale must be one positive finite number per group ({n_groups},)') from e
+      if scale.shape != (n_groups,):
+        raise ValueError(f'{what}: scale must hold one divisor per group ({n_groups},); got {scale.shape}')
+      if not (np.all(np.isfinite(scale)) and np.all(scale > 0)):
+        raise ValueError(f'{what}: scale must be finite and > 0')
+    observed = None if f.y is None else group_target_sums(f.y, f.seg_offsets, f.seg_rows)
+    if observed is not None and not np.isfinite(observed).any():
+      raise ValueError(f'{what}: no group has an observed total: every group holds a NaN target')
+    out = f.run(inference.scenario_summaries, k=int(k), norm=int(norm), scale=scale, observed=observed)
+    res = {'keys': f.keys, 'scenarios': out['scenarios'], 'probability': out['probability'], 'path': out['path'],
+           'distance': out['distance'], 'assignment': out['assignment']}
+    return res, out, observed
+
+  def predict_scenarios(self, table, group_by, k=10, norm=2, scale=None, num_samples=1000, seed=0, weights=None):
+    """The joint sample paths of `predict_samples(table, num_samples, seed, group_by=group_by)` reduced to k representative
+    scenarios, each with a probability -- "three futures" for a staffing plan, a stochastic programme or a stress test --
+    on the GPU: the (num_samples, G) matrix of totals never leaves the device.  Every scenario is an actual path of the
+    forecast, so every group of it stays coherent with the others.  The method is fast forward selection (Heitsch &
+    Roemisch 2003): greedily the paths that minimise the Kantorovich (Wasserstein-1) distance between the ensemble and the
+    scenario set, every other path handing its probability to its nearest scenario (the earliest chosen among equally
+    near).  The distance between two paths is the `norm`-norm (1 or 2) of the difference of their totals.  -> dict:
+      'keys'                       the groups, as in `predict_samples`
+      'scenarios' (k, G)           the totals of the chosen paths, in the order chosen (the first is the ensemble's medoid)
+      'probability' (k,)           the share of the sample paths each scenario stands for; sums to 1
+      'path' (k,) int              the index of each scenario among the sample paths: `predict_samples(table, num_samples,
+                                   seed, group_by=group_by, weights=weights)[0][path]` is 'scenarios', and without group_by
+                                   it gives the scenarios row by row
+      'distance' (k,)              the Kantorovich distance between the ensemble and the first 1 .. k scenarios,
+                                   nonincreasing: how much the ensemble loses, and so where to stop
+      'assignment' (num_samples,)  the scenario of every sample path
+    scale: None, or one positive finite number per group that divides the group's total before the distance is formed,
+    e.g. `predict_dependence(...)['std']` or a population, so that no large group decides alone.  Paths that repeat
+    (totals of counts do) have distance 0: once every distinct path is chosen the rest are taken in index order with
+    probability 0.  1 <= k <= num_samples <= 4,096.  Out of scope: scenarios of single rows over more than 4,096 paths,
+    scenarios of `combinations=`, backward reduction, and a k-medoids refinement of the greedy set.
+    weights: member weights of the sample paths as in `predict_samples`; None: equal weights."""
+    return self._scenario_summaries('predict_scenarios', table, group_by, k, norm, scale, num_samples, seed, weights)[0]
+
+  def score_scenarios(self, table, group_by, k=10, norm=2, scale=None, num_samples=1000, seed=0, weights=None):
+    """`predict_scenarios` held against the totals observed in `table[target_col]`: how near the scenario set comes to what
+    happened, on the GPU.  A group with a NaN target among its rows has no observed total and is left out of EVERY
+    distance, between paths as well, so that the observed vector and the paths are measured alike; at least one group must
+    have one.  -> the dict of `predict_scenarios` ('scenarios' holds all groups) plus
+      'observed' (G,)          sum of the target over the group's rows; NaN when any row of the group has a NaN target
+      'n'                      groups with an observed total
+      'nearest'                the scenario (0 .. k - 1) nearest to the observed vector
+      'nearest_distance'       its distance to the observed vector
+      'pit' (2,)               the shares of the sample paths whose distance to their own scenario is <= and <
+                               'nearest_distance': near 1, the observed lies farther from every scenario than nearly every
+                               path of the forecast does
+    The target checks are those of `score_totals`; the limits, `scale`, what is out of scope and `weights` those of
+    `predict_scenarios`."""
+    res, out, observed = self._scenario_summaries('score_scenarios', table, group_by, k, norm, scale, num_samples, seed,
+                                                  weights, target=True)
+    res.update(observed=observed, n=int(np.isfinite(observed).sum()), nearest=out['nearest'],
+               nearest_distance=out['nearest_distance'], pit=out['pit'])
     return res
 
   @staticmethod

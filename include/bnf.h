@@ -740,6 +740,63 @@ int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, i
                             const double* pair_w, double* mean, double* cov, double* vario, void* work, size_t work_bytes,
                             double* score);
 
+/* A few representative SCENARIOS out of the joint sample paths: whole paths of the ensemble, each with a probability, and
+ * what the ensemble loses by them -- fast forward selection (Heitsch & Roemisch 2003), which greedily picks the paths that
+ * minimise the Kantorovich (Wasserstein-1) distance between the S equally likely paths and the chosen ones with optimally
+ * redistributed mass.  x as for bnf_sample_summaries, S = n_samples, C = n_cols.
+ * bnf_sample_distances: dist DEVICE (S, S) f64, the pairwise distances of the paths.  A column takes part when y is NULL or
+ *   y_c is finite (the rule of bnf_sample_energy_score).  The term of column c for the pair (s, t) is d = x_sc - x_tc, and
+ *   with scale DEVICE (C,) f64 d / scale_c: one IEEE division of the DIFFERENCE (a total of 1e9 with a spread of 10 loses
+ *   nothing; the error of a term is relative to the term).  scale is not validated (reading it would cost a sync): a bad
+ *   scale gives meaningless distances, never an access outside x / scale.
+ *     p = 1: dist[s][t] = sum_c |term_c|          p = 2: dist[s][t] = sqrt(sum_c term_c * term_c)
+ *   the sum over the participating columns in ascending order, ONE sequential f64 sum per cell, a product never contracted
+ *   into the addition that follows: a cell's bits depend on its two paths and the participating columns only, not on S,
+ *   the other paths or the tile geometry.  The matrix is written whole; dist[s][t] and dist[t][s] have the same bits; the
+ *   diagonal is computed like any other cell: +0.0, or NaN for a path that holds a NaN in a participating column (such a
+ *   path is NaN in its whole row and column).  No participating column: every cell is +0.0.
+ *   ydist DEVICE (S,) f64: the same distance between path s and y DEVICE (C,) f64, the same sum; y and ydist are NULL
+ *   together (BNF_ERR_INVALID otherwise).  n_samples <= BNF_SCENARIO_MAX_SAMPLES (a matrix of 128 MiB, the size
+ *   BNF_PAIR_MATRIX_MAX_COLS allows); BNF_ERR_INVALID with nothing launched above that, for n_samples < 1, n_cols < 1, p
+ *   outside {1, 2} and a NULL x or dist.  No work buffer.  S^2 C / 2 differences in 64 x 64 tiles of pairs on and above the
+ *   diagonal, the mirrored tile stored through LDS in whole rows.
+ * bnf_scenario_select: forward selection on a SYMMETRIC dist DEVICE (S, S) f64 (read by rows).  With dmin^0_s = +inf, for
+ *   step i = 1 .. k:
+ *     z_i(u) = sum_s min(dmin^(i-1)_s, dist[s][u])   for every path u not yet chosen
+ *     chosen[i - 1] = u_i, the u with the smallest z_i, the LOWEST INDEX among equal ones
+ *     dmin^i_s = min(dmin^(i-1)_s, dist[s][u_i])
+ *     objective[i - 1] = z_i(u_i) / (double)S: the very sum that won, divided once -- the Kantorovich distance between
+ *       the ensemble and the first i scenarios; nonincreasing in i
+ *   and after step k
+ *     assign DEVICE (S,) int32 or NULL: the smallest j in 0 .. k - 1 with dist[s][chosen[j]] == dmin^k_s (among equally
+ *       near scenarios the earliest chosen)       nearest DEVICE (S,) f64 or NULL: dmin^k_s
+ *     prob DEVICE (k,) f64: #{s : assign[s] = j} / (double)S
+ *   Identical paths have distance 0 (totals of counts repeat all the time): once every distinct path is chosen all
+ *   remaining candidates tie, and the lowest unchosen index is taken with probability 0.  That is defined, not an error.
+ *   ydist DEVICE (S,) f64 or NULL, as bnf_sample_distances writes it; with it (obs_nearest and obs are required then, and
+ *   ignored without):
+ *     obs_nearest DEVICE (1,) int32: the earliest chosen j that minimises ydist[chosen[j]]       obs DEVICE (3,) f64:
+ *     obs[0] that distance; obs[1] = #{s : nearest_s <= obs[0]} / S; obs[2] = #{s : nearest_s < obs[0]} / S -- the PIT of the
+ *     observed vector's distance to the scenario set among the paths' own (near 1: the observed lies farther from every
+ *     scenario than nearly every path of the forecast does)
+ *   A NaN cell anywhere in dist: chosen, assign and obs_nearest are -1 everywhere and objective, prob, nearest and obs NaN
+ *   (a first kernel sets a device flag the later ones read; the host never waits for it).
+ *   The sum z_i(u) over s is in an order S alone fixes: with 256 threads, thread t adds s = t, t + 256, ... in that order,
+ *   then the wave butterfly (v += shfl_xor(v, off), off = 32 .. 1), then the four waves in order.  All k steps are
+ *   enqueued back to back; the pick of a step stays on the device.  S^2 reads of dist per step.
+ *   work DEVICE, work_bytes: dmin and z (S f64 each), the taken marks (S int32), the flag and the pick:
+ *     20 * n_samples + 16 bytes, 8-byte aligned; BNF_ERR_INVALID below that
+ *   1 <= k <= n_samples <= BNF_SCENARIO_MAX_SAMPLES; BNF_ERR_INVALID otherwise and for a NULL dist, work, chosen, objective
+ *   or prob, with nothing launched.
+ * Both: everything is f64, no floating-point atomics, two calls give the same bits; they run on the handle's stream, do not
+ * touch the training state, work on forward-only handles; the observation model of the handle plays no part. */
+#define BNF_SCENARIO_MAX_SAMPLES 4096
+int bnf_sample_distances(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
+                         const double* y, int32_t p, double* dist, double* ydist);
+int bnf_scenario_select(bnf_handle* h, const double* dist, int64_t n_samples, int32_t k, const double* ydist, void* work,
+                        size_t work_bytes, int32_t* chosen, double* objective, double* prob, int32_t* assign,
+                        double* nearest, int32_t* obs_nearest, double* obs);
+
 /* How the columns of the joint sample paths RANK against each other within a path -- "which groups are among the k
  * largest" -- which no marginal shows.  x as for bnf_sample_summaries, S = n_samples, G = n_cols.
  * bnf_sample_ranks: per path s the ranked values are v_sg = x_sg / scale_g, a plain IEEE f64 division, with
