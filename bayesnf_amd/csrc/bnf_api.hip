@@ -1275,7 +1275,9 @@ static void group_passes(const bnf_handle* h, int64_t n_samples, int64_t chunk, 
 }
 
 // the launch shape of the sample-path kernels: x = blocks of `per_block` rows (positions), y = the samples, strided; the
-// combine kernel of a group reduction (one wave per tile and sample) takes (grid.x, cdiv(S, 4))
+// combine kernel of a group reduction (one wave per tile and sample) takes (grid.x, cdiv(S, 4)).
+// tests/test_gpu_sampler_law.py restates gy (group_sums_sample_stride) to test the totals for correlation at that lag:
+// change both together.
 static dim3 pred_grid(int64_t R, int64_t per_block, int64_t S) {
   const int64_t gx = cdiv(R, per_block);
   const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));

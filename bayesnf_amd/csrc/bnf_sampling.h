@@ -20,6 +20,10 @@
 //                         uniform of the shape < 1 boost (the one of the accepted trial is used)
 //       slot 2, trial t : Poisson: trial 0 word 0 is the inversion uniform (rate < 10); PTRS proposal t takes words 0, 1
 //
+// Non-finite parameters: a NaN in loc, or in the aux entry the model reads (NORMAL aux[0]; NB aux[1]; ZINB aux[1], aux[2]),
+// of the drawn member gives a NaN draw -- never a count, and the zero inflation does not hide it; a rate beyond the f32
+// range gives +inf (in the ZINB, where the inflation has not put its 0).  No finite draw depends on these tests.
+//
 // Bounded loops: every rejection loop stops after kPredMaxTrials = 64 proposals and takes the last one that lay inside the
 // support.  Marsaglia-Tsang rejects with probability < 0.05 (shape >= 1), PTRS with probability < 0.25 (rate >= 10):
 // reaching the cap has probability < 0.25^64 = 3e-39 per draw.  The inversion loop ends at k = 64 at the latest
@@ -105,9 +109,11 @@ __device__ __forceinline__ float pred_poisson_logpmf(float k, float lam, float l
 }
 
 // Poisson(lam) as a float.  lam < 10: sequential inversion of one uniform.  Else Hoermann's transformed rejection
-// with squeeze (PTRS, 1993).  Counts above 2^24 come out rounded to the nearest float.
+// with squeeze (PTRS, 1993).  Counts above 2^24 come out rounded to the nearest float.  A NaN rate is returned as it is
+// (it would fail every compare of the inversion loop and come out as the count 0); the rate +inf comes out as +inf.
 __device__ __forceinline__ float pred_poisson(uint64_t seed, uint32_t s, uint64_t r, float lam) {
 #pragma clang fp contract(off)
+  if (lam != lam) return lam;
   if (!(lam >= kPredInvRate)) {
     const Philox b = pred_bits(seed, s, r, PRED_SLOT_POISSON, 0);
     const float u = u01_open(b.v[0]);
@@ -152,8 +158,9 @@ __device__ __forceinline__ float predictive_draw(uint64_t seed, uint32_t s, uint
     return loc + a0 * std_normal(b.v[0], b.v[1]);
   }
   if constexpr (OBS == BNF_OBS_ZINB) {
+    if (a2 != a2) return a2;                       // a NaN inflation probability fails the compare: it would never inflate
     const Philox b = pred_bits(seed, s, r, PRED_SLOT_BASE, 0);
-    if (u01_open(b.v[2]) < a2) return 0.f;
+    if (u01_open(b.v[2]) < a2) return (loc != loc || a1 != a1) ? loc + a1 : 0.f;   // NaN parameters: a NaN, not the 0
   }
   const float logits = -logf(a1) - logf(softplusf(loc));
   const float lrate = pred_log_gamma(seed, s, r, 1.f / a1) + logits;

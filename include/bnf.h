@@ -280,6 +280,9 @@ int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* au
  * log softplus(loc), drawn as Poisson(Gamma(total_count, scale e^logits)); ZINB: 0 with probability aux[2]).
  *   loc DEVICE (n_members, n_rows) and aux DEVICE (n_members, 3) as written by bnf_forward
  *   out DEVICE (n_samples, n_rows) f32 (counts above 2^24 rounded to the nearest float)
+ *   NaN: a NaN parameter of the drawn member gives a NaN draw; a rate beyond the f32 range gives +inf.  The parameters
+ *     are loc[c_s, r] (that row only) and the aux entries the model reads (NORMAL aux[0]; NB aux[1]; ZINB aux[1], aux[2]:
+ *     every row of the path); the zero inflation does not replace a NaN, and keeps its 0 beside +inf.
  *   row0, sample0: global index of loc's first column / of out's first row.  The value at (sample s, row r) is a pure
  *     function of (seed, sample0 + s, row0 + r, loc[c_s, r], aux[c_s]): a caller may cut rows and samples into chunks of
  *     any size and gets the bits of the one big call.  row0 + n_rows <= 2^56, sample0 + n_samples <= 2^32.

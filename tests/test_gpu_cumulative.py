@@ -1,6 +1,7 @@
 """Running totals of the sample paths and when they pass a level, on the GPU (include/bnf.h
 bnf_predictive_group_cumulative) against the naive loop of tests/cumulative_ref.py (np.cumsum in float64) on
-`Engine.predictive_samples` for the same seed.  NB / ZINB: every sum is an exact integer, every comparison is EXACT.
+`Engine.predictive_samples` for the same seed.  NB / ZINB: every sum is an exact integer, every comparison is EXACT
+(a NaN draw, from a NaN parameter, makes the same cells NaN on both sides).
 NORMAL: |running - ref| <= n 2^-52 cumsum(|x|) with n the participating positions so far -- twice the standard bound
 gamma_{n-1} sum |x| of a float64 sum in any order; nothing is measured -- and the crossing outputs are exactly those
 recomputed on the host from the GPU's own running totals.  The engine-level tests use synthetic loc / aux on a
@@ -60,7 +61,7 @@ def _check(tag, obs, got, x, off, rows, level):
   else:
     for k in ('running', 'total'):
       if k in got:
-        assert np.array_equal(got[k], ref[k]), (tag, k, int((got[k] != ref[k]).sum()))
+        assert np.array_equal(got[k], ref[k], equal_nan=True), (tag, k, int((got[k] != ref[k]).sum()))
   if level is None:
     assert not set(CROSSING) & set(got), (tag, 'crossing outputs without a level')
     return ref
@@ -91,7 +92,7 @@ def _check(tag, obs, got, x, off, rows, level):
 def test_mixed_and_crossing_tiles(obs, kind):
   """Tiles inside one group, mixed tiles and groups that cross tile edges; the rows of every group in a random order
   (time is position order, not row order).  The level of a group is half the median of its reference totals.  A few rows
-  carry a NaN location: NORMAL draws NaN there, which makes every later running total of the group NaN."""
+  carry a NaN location: every model draws NaN there, which makes every later running total of the group NaN."""
   eng, _ = _engine(obs)
   M, R, n = 4, 3 * TILE + 37, 16
   rng = np.random.default_rng(5)
@@ -104,7 +105,7 @@ def test_mixed_and_crossing_tiles(obs, kind):
   assert not np.array_equal(rows, inference.csr_from_codes(codes, G)[1])
   loc_d, aux_d = _dev(eng, loc), _dev(eng, aux)
   x = eng.predictive_samples(loc_d, aux_d, n, seed=42).cpu().numpy()
-  assert obs != 'NORMAL' or np.isnan(x[:, nan_rows]).all()
+  assert np.isnan(x[:, nan_rows]).all() and np.isnan(x).sum() == n * len(np.unique(nan_rows))
   level = _half_median_level(Cu.group_cumulative(x, off, rows)['total'])
   call = lambda **kw: _host(eng.predictive_group_cumulative(loc_d, aux_d, off, rows, n, 42, **kw))
   got = call(level=level, running=True)
@@ -124,12 +125,18 @@ def test_mixed_and_crossing_tiles(obs, kind):
   # running total stayed above its level once it is there
   size = np.where(np.diff(off) > 0, ref['steps'][np.maximum(np.asarray(off[1:]) - 1, 0)], 0)
   after = int((size[None, :] - got['cross_step'])[crossed].sum())
+  assert np.isnan(got['total'][:, big]).all() and np.isnan(got['running']).sum() > n * 4
   if obs == 'NORMAL':
-    assert np.isnan(got['total'][:, big]).all() and np.isnan(got['running']).sum() > n * 4
     assert 0 < got['above_count'].sum() < after, 'NORMAL: running totals come back under the level (or turn NaN)'
   else:
-    assert got['above_count'].sum() == after, 'counts: a running total never comes back'
-    assert np.array_equal(got['total'], sums), 'total against predictive_group_sums'
+    # in the groups without a NaN row; those with one are held to the reference above, cell by cell
+    clean = ~np.isin(np.arange(G), codes[nan_rows])
+    after_clean = int((size[None, :] - got['cross_step'])[crossed & clean[None, :]].sum())
+    assert clean.sum() >= G - 3 and 0 < after_clean <= after
+    assert got['above_count'][clean[codes]].sum() == after_clean, 'counts: a running total never comes back'
+    assert got['above_count'][~clean[codes]].sum() <= after - after_clean, 'a NaN running total is not above its level'
+    assert np.array_equal(got['total'], sums, equal_nan=True), 'total against predictive_group_sums'
+    assert np.array_equal(np.isnan(sums), np.broadcast_to(~clean, (n, G))), 'the totals of the groups with a NaN row'
   for k in got:
     assert _same(got[k], again[k]), ('two runs differ', k)
   for k in bare:
