@@ -1,4 +1,6 @@
-// bnf_api.hip -- host engine + C ABI (include/bnf.h) of libbnf_hip.so.
+// bnf_api.hip -- the training engine of libbnf_hip.so and its share of the C ABI (include/bnf.h): the handle, the
+// train step, bnf_forward, the validation check, the debug and profile calls.  The forecast entry points are
+// bnf_forecast.hip and the RCCL loader is bnf_comm.cpp; the three units share bnf_host.h.
 //
 // The reference runs a whole fit() as ONE XLA program (inference.py:621 is the
 // single host->device dispatch).  Here the C side enqueues every kernel of every
@@ -16,8 +18,6 @@
 #include <rocprim/device/device_radix_sort.hpp>            // the stable key-value sort of jax.random.permutation
 #include <rocprim/device/device_segmented_radix_sort.hpp>  // (bnf_row_keys): the one library primitive in here
 
-#include <dlfcn.h>
-
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -29,47 +29,27 @@
 #include <vector>
 
 #include "../../include/bnf.h"
+#include "bnf_host.h"
 #include "bnf_gemm.h"
 #include "bnf_kernels.h"
 #include "bnf_panel.h"
 #include "bnf_gemm8.h"
-#include "bnf_sampling.h"
-#include "bnf_combinations.h"
-#include "bnf_extremes.h"
-#include "bnf_episodes.h"
-#include "bnf_cumulative.h"
-#include "bnf_windows.h"
-#include "bnf_scoring.h"
-#include "bnf_rps.h"
-#include "bnf_totals.h"
-#include "bnf_dependence.h"
-#include "bnf_ranking.h"
-#include "bnf_bands.h"
-#include "bnf_scenarios.h"
-#include "bnf_stacking.h"
 #include "bnf_validation.h"
 #include "bnf_plan.h"
 
 using namespace bnf;
 
 // ---------------------------------------------------------------------------
-// errors
+// errors (bnf_host.h: the one definition of fail(), for every unit)
 // ---------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-#define HIPCHK(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess)                                                              \
-      return fail(BNF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                  __FILE__, __LINE__);                                                 \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // kernel ids for the event timer
@@ -338,20 +318,6 @@ static void phase_prof_end(bnf_handle* h, int kid, unsigned blocks, int threads)
 #endif
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: remember per
-// (kernel instantiation, device) that it has been raised (a process may drive several GPUs).
-template <typename K>
-static void allow_lds(bnf_handle* h, K kernel, int bytes, std::atomic<uint64_t>* done_mask) {
-  // (atomic: one host thread per device enqueues through the same launchers -- distributed.run_shards)
-  const uint64_t bit = 1ull << (h->cfg.device & 63);
-  if (done_mask->load(std::memory_order_relaxed) & bit) return;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess)
-    fprintf(stderr, "[bnf] hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed: %s\n", bytes, hipGetErrorString(e));
-  done_mask->fetch_or(bit, std::memory_order_relaxed);
-}
-
 template <typename T, int EPI, int TAG, int WGM, int WGN>
 static void launch_gemm_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep) {
   constexpr int kLds = Mma<T>::lds_bytes(WGM, WGN, epi_extra_lds(EPI, WGM, WGN, (int)sizeof(T)));
@@ -364,7 +330,7 @@ static void launch_gemm_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
       // B is a packed Dense kernel (split when packed: k_pack_weights) everywhere but in the test entry's plain product
       constexpr int kS = EPI == EPI_PLAIN ? 1 : 2;
       static std::atomic<uint64_t> attr_done_s{0};
-      allow_lds(h, &gemm_nt<T, EPI, TAG, WGM, WGN, kS>, kLds, &attr_done_s);
+      allow_lds(h->cfg.device, &gemm_nt<T, EPI, TAG, WGM, WGN, kS>, kLds, &attr_done_s);
       const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
       EpiArgs ep2 = ep;
       ep2.ablate = h->sw.ablate;
@@ -378,7 +344,7 @@ static void launch_gemm_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
     }
   }
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &gemm_nt<T, EPI, TAG, WGM, WGN>, kLds, &attr_done);
+  allow_lds(h->cfg.device, &gemm_nt<T, EPI, TAG, WGM, WGN>, kLds, &attr_done);
   const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
   EpiArgs ep2 = ep;
   ep2.ablate = h->sw.ablate;
@@ -440,7 +406,7 @@ static void launch_gemm_tn_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs&
   if constexpr (std::is_same<T, float>::value) {
     if (h->f32_split) {      // BNF_DTYPE_F32S
       static std::atomic<uint64_t> attr_done_s{0};
-      allow_lds(h, &gemm_tn<T, TAG, WG, true>, kLds, &attr_done_s);
+      allow_lds(h->cfg.device, &gemm_tn<T, TAG, WG, true>, kLds, &attr_done_s);
       const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
       LaunchScope ls(h, kid, st, true);
       hipLaunchKernelGGL((gemm_tn<T, TAG, WG, true>), dim3(blocks), dim3(64 * WG * WG), kLds, st, g, ep);
@@ -448,7 +414,7 @@ static void launch_gemm_tn_wg(bnf_handle* h, int kid, GemmArgs g, const EpiArgs&
     }
   }
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &gemm_tn<T, TAG, WG>, kLds, &attr_done);
+  allow_lds(h->cfg.device, &gemm_tn<T, TAG, WG>, kLds, &attr_done);
   const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk);
   LaunchScope ls(h, kid, st, true);
   hipLaunchKernelGGL((gemm_tn<T, TAG, WG>), dim3(blocks), dim3(64 * WG * WG), kLds, st, g, ep);
@@ -459,7 +425,7 @@ static void launch_gemm_tn_skinny(bnf_handle* h, int kid, GemmArgs g, const EpiA
   g.tiles_n = g.N / 512;
   if (g.splitk < 1) g.splitk = 1;
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &gemm_tn_skinny, kSkLds, &attr_done);
+  allow_lds(h->cfg.device, &gemm_tn_skinny, kSkLds, &attr_done);
   const unsigned blocks = (unsigned)((int64_t)g.members * g.tiles_n * g.splitk);
   LaunchScope ls(h, kid, st, true);
   hipLaunchKernelGGL(gemm_tn_skinny, dim3(blocks), dim3(512), kSkLds, st, g, ep);
@@ -476,7 +442,7 @@ static void launch_gemm_tn_skinny_featbwd(bnf_handle* h, int kid, GemmArgs g, co
   fw.F = h->F; fw.off_lsa = h->nd.off_lsa; fw.n_groups = h->nd.n_groups; fw.n_inputs = h->nd.D;
   fw.scal_stride = kScalStride; fw.scal_gfac = kScalGfac; fw.scal_sp_in = kScalGroup + h->fb.in_group;
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &gemm_tn_skinny_featbwd, kSkLdsFb, &attr_done);
+  allow_lds(h->cfg.device, &gemm_tn_skinny_featbwd, kSkLdsFb, &attr_done);
   const unsigned blocks = (unsigned)((int64_t)g.members * g.tiles_n * g.splitk);
   LaunchScope ls(h, kid, st, true);
   hipLaunchKernelGGL(gemm_tn_skinny_featbwd, dim3(blocks), dim3(512), kSkLdsFb, st, g, ep, fw);
@@ -500,10 +466,10 @@ static void launch_gemm_tn(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& ep
       ep2.ablate = h->sw.ablate;
       LaunchScope ls(h, kid, st, true);
       if (g.splitk == 1) {   // plain stores: accumulators transposed, 16-byte stores
-        allow_lds(h, &gemm_tn_ring<TAG, true>, kRgLds, &attr_done_s);
+        allow_lds(h->cfg.device, &gemm_tn_ring<TAG, true>, kRgLds, &attr_done_s);
         hipLaunchKernelGGL((gemm_tn_ring<TAG, true>), dim3(blocks), dim3(512), kRgLds, st, g, ep2);
       } else {
-        allow_lds(h, &gemm_tn_ring<TAG, false>, kRgLds, &attr_done);
+        allow_lds(h->cfg.device, &gemm_tn_ring<TAG, false>, kRgLds, &attr_done);
         hipLaunchKernelGGL((gemm_tn_ring<TAG, false>), dim3(blocks), dim3(512), kRgLds, st, g, ep2);
       }
       return;
@@ -527,28 +493,26 @@ static void launch_gemm_tn8(bnf_handle* h, int kid, GemmArgs g, const EpiArgs& e
   if (kind == WG_SKINNY && TAG == 0) {
     g.tiles_m = 1; g.tiles_n = g.N / 512;
     static std::atomic<uint64_t> attr_done{0};
-    allow_lds(h, &gemm_tn_skinny8, kSk8Lds, &attr_done);
+    allow_lds(h->cfg.device, &gemm_tn_skinny8, kSk8Lds, &attr_done);
     hipLaunchKernelGGL(gemm_tn_skinny8, dim3((unsigned)((int64_t)g.members * g.tiles_n * g.splitk)), dim3(512), kSk8Lds, st, g, ep2);
   } else if (kind == WG_RING) {
     g.tiles_m = g.M / 256; g.tiles_n = g.N / 256;
     static std::atomic<uint64_t> attr_done{0}, attr_done_s{0};
     const unsigned blocks = (unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk * (g.n_multi > 1 ? g.n_multi : 1));
     if (g.splitk == 1) {
-      allow_lds(h, &gemm_tn_ring8<TAG, true>, kRgLds, &attr_done_s);
+      allow_lds(h->cfg.device, &gemm_tn_ring8<TAG, true>, kRgLds, &attr_done_s);
       hipLaunchKernelGGL((gemm_tn_ring8<TAG, true>), dim3(blocks), dim3(512), kRgLds, st, g, ep2);
     } else {
-      allow_lds(h, &gemm_tn_ring8<TAG, false>, kRgLds, &attr_done);
+      allow_lds(h->cfg.device, &gemm_tn_ring8<TAG, false>, kRgLds, &attr_done);
       hipLaunchKernelGGL((gemm_tn_ring8<TAG, false>), dim3(blocks), dim3(512), kRgLds, st, g, ep2);
     }
   } else {
     g.tiles_m = (g.M + 127) / 128; g.tiles_n = (g.N + 127) / 128;
     static std::atomic<uint64_t> attr_done{0};
-    allow_lds(h, &gemm_tn8<TAG>, kTn8Lds, &attr_done);
+    allow_lds(h->cfg.device, &gemm_tn8<TAG>, kTn8Lds, &attr_done);
     hipLaunchKernelGGL((gemm_tn8<TAG>), dim3((unsigned)(g.members * g.tiles_m * g.tiles_n * g.splitk)), dim3(256), kTn8Lds, st, g, ep2);
   }
 }
-
-static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------
 // pipeline pieces, templated on the storage type
@@ -605,7 +569,7 @@ static void run_forward(bnf_handle* h, const float* theta, int nmem, const RowSr
     dim3 grid(cdiv(rows, kFeatRows) * (unsigned)nmem);
     const size_t lds = (size_t)kFeatRows * (h->Fp + 16 / h->es) * h->es;
     static std::atomic<uint64_t> attr_done{0};
-    allow_lds(h, &k_featurize<T>, 160 * 1024, &attr_done);
+    allow_lds(h->cfg.device, &k_featurize<T>, 160 * 1024, &attr_done);
     hipLaunchKernelGGL((k_featurize<T>), grid, dim3(kFeatRows), lds, h->stream, h->nd, rs, X, stab,
                        y, h->scal, rows, (T*)h->H0, Bp * h->Fp,
                        (T*)nullptr, (int64_t)h->Fp * Bp, (int32_t)Bp,
@@ -878,7 +842,7 @@ static void launch_panel_form(bnf_handle* h, const PanelArgs& pa) {
   constexpr int kLds = panel_lds_bytes(WN, RT, H0L, CH, FP);
   static_assert(kLds <= 160 * 1024, "LDS per workgroup");
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW>, kLds, &attr_done);
+  allow_lds(h->cfg.device, &k_panel_fwd_bwd<WN, RT, H0L, DEEP, CH, FP, F0, C8, FBW>, kLds, &attr_done);
   PanelArgs pa2 = pa;
   pa2.ablate = h->sw.ablate;
   const unsigned blocks = (unsigned)(pa.members * pa.panels);
@@ -914,7 +878,7 @@ static void run_panel(bnf_handle* h, const float* theta, int nmem, const RowSrc&
     dim3 grid(cdiv(h->B, kFeatRows) * (unsigned)nmem);
     const size_t lds = (size_t)kFeatRows * (h->Fp + 8) * 2;
     static std::atomic<uint64_t> attr_done{0};
-    allow_lds(h, &k_featurize<bf16_t>, 160 * 1024, &attr_done);
+    allow_lds(h->cfg.device, &k_featurize<bf16_t>, 160 * 1024, &attr_done);
     hipLaunchKernelGGL((k_featurize<bf16_t>), grid, dim3(kFeatRows), lds, h->stream, h->nd, rs, h->X, h->stab,
                        h->y, h->scal, h->B, (bf16_t*)h->H0, Bp * h->Fp, (bf16_t*)h->H0t,
                        (int64_t)h->Fp * Bp, (int32_t)Bp, h->ybat, Bp, (int32_t)nmem, (int32_t)(h->pp.fold0 ? 2 : 0), h->H0q);
@@ -1252,93 +1216,15 @@ static int step_vi(bnf_handle* h, int64_t step, float* loss, int64_t loss_stride
   return BNF_OK;
 }
 
+// All the forecast unit (bnf_forecast.hip) sees of a handle, read from it at call time (bnf_host.h)
+Forecast forecast_view(const bnf_handle* h) {
+  if (!h) return Forecast{false, 0, 0, nullptr, nullptr};
+  return Forecast{h->bound, h->cfg.device, h->cfg.obs_model, h->stream, h->qscratch};
+}
+
 // ---------------------------------------------------------------------------
-// C ABI
+// C ABI: the engine's share (the forecasts: bnf_forecast.hip; the posterior gather: bnf_comm.cpp)
 // ---------------------------------------------------------------------------
-// the observation model of the handle as a compile-time constant: f(tag) with decltype(tag)::value the BNF_OBS_* code
-template <typename F>
-static void with_obs(const bnf_handle* h, F&& f) {
-  switch (h->cfg.obs_model) {
-    case BNF_OBS_NORMAL: f(std::integral_constant<int, BNF_OBS_NORMAL>{}); break;
-    case BNF_OBS_NB: f(std::integral_constant<int, BNF_OBS_NB>{}); break;
-    default: f(std::integral_constant<int, BNF_OBS_ZINB>{}); break;
-  }
-}
-
-// the passes of a group reduction through its work buffer, `chunk` sample paths each (group_chunk): launch(obs, s0, n)
-// enqueues the n paths from s0 on, obs as in with_obs
-template <typename F>
-static void group_passes(const bnf_handle* h, int64_t n_samples, int64_t chunk, F&& launch) {
-  with_obs(h, [&](auto obs) {
-    for (int64_t s0 = 0; s0 < n_samples; s0 += chunk) launch(obs, s0, std::min(chunk, n_samples - s0));
-  });
-}
-
-// the launch shape of the sample-path kernels: x = blocks of `per_block` rows (positions), y = the samples, strided; the
-// combine kernel of a group reduction (one wave per tile and sample) takes (grid.x, cdiv(S, 4)).
-// tests/test_gpu_sampler_law.py restates gy (group_sums_sample_stride) to test the totals for correlation at that lag:
-// change both together.
-static dim3 pred_grid(int64_t R, int64_t per_block, int64_t S) {
-  const int64_t gx = cdiv(R, per_block);
-  const int64_t gy = std::min<int64_t>(std::min<int64_t>(S, 65535), std::max<int64_t>(1, 16384 / gx));
-  return dim3((unsigned)gx, (unsigned)gy);
-}
-
-// posterior-predictive sampling launches (bnf_sampling.h), one instantiation per observation model
-template <int OBS>
-static void launch_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t M, int64_t R, int64_t S,
-                                      uint64_t seed, int64_t row0, int64_t sample0, const double* cum, float* out) {
-  hipLaunchKernelGGL((k_predictive_samples<OBS>), pred_grid(R, 256 * kPredRowsPerThread, S), dim3(256), 0, h->stream, loc,
-                     aux, (int32_t)M, R, S, seed, row0, sample0, cum, out);
-}
-
-// held-out scoring launches (bnf_scoring.h), one instantiation per observation model and for the member weights wts
-// (WEIGHTED: wts non-null, no member_ll)
-template <int OBS, bool WEIGHTED>
-static void launch_predictive_scores(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t M,
-                                     int64_t R, const float* y, double* ll_partial, double* pair_partial, int64_t n_slots, double* member_ll,
-                                     float* lpd, float* pit, float* crps) {
-  const int64_t nt = cdiv(R, kScoreTile);
-  if (member_ll) {
-    hipLaunchKernelGGL((k_score_member_ll<OBS>), dim3((unsigned)nt, (unsigned)std::min<int64_t>(M, 65535)), dim3(256), 0,
-                       h->stream, loc, aux, (int32_t)M, R, y, ll_partial);
-    hipLaunchKernelGGL(k_score_member_ll_combine, dim3(cdiv(M, 4)), dim3(256), 0, h->stream, ll_partial, (int32_t)M, nt,
-                       member_ll);
-  }
-  if (crps)
-    hipLaunchKernelGGL((k_score_crps_pairs<WEIGHTED>), dim3((unsigned)nt, (unsigned)n_slots), dim3(256), 0, h->stream, loc,
-                       aux, wts, (int32_t)M, R, pair_partial);
-  if (lpd || crps || (pit && OBS == BNF_OBS_NORMAL))
-    hipLaunchKernelGGL((k_score_rows<OBS, WEIGHTED>), dim3(cdiv(R, 64)), dim3(64), 0, h->stream, loc, aux, wts, (int32_t)M, R, y,
-                       pair_partial, (int32_t)n_slots, lpd, pit, crps);
-  if (pit && OBS != BNF_OBS_NORMAL)
-    hipLaunchKernelGGL((k_score_count_pit<WEIGHTED>), dim3(cdiv(R, 64), 2), dim3(64), 0, h->stream, loc, aux, wts, (int32_t)M, R,
-                       (int32_t)OBS, y, pit);
-}
-
-// ranked probability score (bnf_rps.h): one wave per row, the rows beyond 2^20 blocks by grid stride
-template <int OBS, bool WEIGHTED>
-static void launch_count_rps(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t M, int64_t R,
-                             const float* y, float* rps) {
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_count_rps<OBS, WEIGHTED>, (int)rps_lds_bytes(BNF_RPS_MAX_MEMBERS), &attr_done);
-  hipLaunchKernelGGL((k_count_rps<OBS, WEIGHTED>), dim3((unsigned)std::min<int64_t>(R, 1 << 20)), dim3(64), rps_lds_bytes(M),
-                     h->stream, loc, aux, wts, (int32_t)M, R, y, rps);
-}
-
-// summaries of sample paths (bnf_totals.h): one workgroup per slab of C adjacent columns, C * P <= 16,384 doubles of LDS
-static void launch_sample_summaries(bnf_handle* h, const double* x, int64_t S, int64_t G, const double* y,
-                                    const SummaryQ& q, double* mean, double* quant, double* crps, double* pit) {
-  int P = 1;
-  while (P < S) P <<= 1;
-  const int C = std::min(kSumMaxCols, kSumMaxSamples / P);
-  const int threads = std::min(1024, std::max(64, C * P / 2));          // a multiple of 64: C * P is a power of two
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_sample_summaries, (int)(sizeof(double) * kSumMaxSamples), &attr_done);
-  hipLaunchKernelGGL(k_sample_summaries, dim3(cdiv(G, C)), dim3(threads), sizeof(double) * (size_t)C * (size_t)P, h->stream,
-                     x, (int32_t)S, G, (int32_t)P, (int32_t)C, y, q, mean, quant, crps, pit);
-}
-
 extern "C" {
 
 int bnf_abi_version(void) { return BNF_ABI_VERSION; }
@@ -1783,461 +1669,6 @@ int bnf_forward(bnf_handle* h, const float* theta, int64_t n_members, const floa
   return BNF_OK;
 }
 
-// wts: the member weights of the *_weighted entry points, DEVICE (n_members,) f64; NULL = the equal-weight kernels
-static int normal_mixture_quantiles_impl(bnf_handle* h, const float* means, const float* scales, const double* wts,
-                                         int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                         int32_t approximate, float* out) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!means || !scales || !q || !out || n_members < 1 || n_rows < 1 || n_q < 0)
-    return fail(BNF_ERR_INVALID, "argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  float* mpart = h->qscratch;
-  float* spart = h->qscratch + 2048;
-  float* bracket = h->qscratch + 4096;
-  if (!approximate) {
-    const int nb_m = (int)std::min<int64_t>(1024, cdiv(n_members * n_rows, 256));
-    const int nb_s = (int)std::min<int64_t>(1024, cdiv(n_members, 256));
-    hipLaunchKernelGGL(k_minmax_partial, dim3(nb_m), dim3(256), 0, h->stream, means,
-                       n_members * n_rows, mpart);
-    hipLaunchKernelGGL(k_minmax_partial, dim3(nb_s), dim3(256), 0, h->stream, scales, n_members, spart);
-    hipLaunchKernelGGL(k_bracket, dim3(1), dim3(64), 0, h->stream, mpart, nb_m, spart, nb_s, bracket);
-  }
-  for (int i = 0; i < n_q; ++i) {
-    float* o = out + (int64_t)i * n_rows;
-    const dim3 grid(cdiv(n_rows, 256));
-    if (approximate && wts)
-      hipLaunchKernelGGL(k_quantile_approx<true>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, q[i], o);
-    else if (approximate)
-      hipLaunchKernelGGL(k_quantile_approx<false>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, q[i], o);
-    else if (wts)
-      hipLaunchKernelGGL(k_quantile_root<true>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, bracket, q[i], o);
-    else
-      hipLaunchKernelGGL(k_quantile_root<false>, grid, dim3(256), 0, h->stream, means, scales, wts, n_members, n_rows, bracket, q[i], o);
-  }
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_normal_mixture_quantiles(bnf_handle* h, const float* means, const float* scales,
-                                 int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                 int32_t approximate, float* out) {
-  return normal_mixture_quantiles_impl(h, means, scales, nullptr, n_members, n_rows, q, n_q, approximate, out);
-}
-
-static int count_mixture_quantiles_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts,
-                                        int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                        float* means, float* out) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (h->cfg.obs_model != BNF_OBS_NB && h->cfg.obs_model != BNF_OBS_ZINB)
-    return fail(BNF_ERR_STATE, "handle's observation model is not NB / ZINB");
-  if (!loc || !aux || !means || n_members < 1 || n_rows < 1 || n_q < 0 || (n_q > 0 && (!q || !out)))
-    return fail(BNF_ERR_INVALID, "argument");
-  for (int i = 0; i < n_q; ++i)
-    if (!(q[i] > 0.f && q[i] < 1.f)) return fail(BNF_ERR_INVALID, "quantile %g outside (0, 1)", q[i]);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  float* part = h->qscratch;
-  float* bracket = h->qscratch + 4096;
-  const int nb = (int)std::min<int64_t>(1024, cdiv(n_members * n_rows, 256));
-  hipLaunchKernelGGL(k_count_moments, dim3(nb), dim3(256), 0, h->stream, loc, aux, n_members, n_rows,
-                     h->cfg.obs_model, means, part);
-  hipLaunchKernelGGL(k_count_bracket, dim3(1), dim3(64), 0, h->stream, part, nb, bracket);
-  for (int i = 0; i < n_q; ++i) {
-    if (wts)
-      hipLaunchKernelGGL(k_count_quantile_root<true>, dim3(cdiv(n_rows, 64)), dim3(64), 0, h->stream, loc, aux, wts,
-                         n_members, n_rows, h->cfg.obs_model, bracket, q[i], out + (int64_t)i * n_rows);
-    else
-      hipLaunchKernelGGL(k_count_quantile_root<false>, dim3(cdiv(n_rows, 64)), dim3(64), 0, h->stream, loc, aux, wts,
-                         n_members, n_rows, h->cfg.obs_model, bracket, q[i], out + (int64_t)i * n_rows);
-  }
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_count_mixture_quantiles(bnf_handle* h, const float* loc, const float* aux,
-                                int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                float* means, float* out) {
-  return count_mixture_quantiles_impl(h, loc, aux, nullptr, n_members, n_rows, q, n_q, means, out);
-}
-
-
-// ---- posterior-predictive sampling (bnf_sampling.h) -----------------------------
-static int predictive_args(const bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                           int64_t n_samples, int64_t row0, int64_t sample0) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!loc || !aux || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL || n_samples < 1)
-    return fail(BNF_ERR_INVALID, "argument");
-  if (row0 < 0 || row0 + n_rows > (1LL << 56)) return fail(BNF_ERR_INVALID, "row0 + n_rows exceeds 2^56");
-  if (sample0 < 0 || sample0 + n_samples > (1LL << 32)) return fail(BNF_ERR_INVALID, "sample0 + n_samples exceeds 2^32");
-  return BNF_OK;
-}
-
-static int predictive_samples_impl(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                   int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, const double* cum,
-                                   float* out) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!out) return fail(BNF_ERR_INVALID, "argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  with_obs(h, [&](auto obs) {
-    launch_predictive_samples<decltype(obs)::value>(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum, out);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_predictive_samples(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                           int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, float* out) {
-  return predictive_samples_impl(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, nullptr, out);
-}
-
-// what the three group reductions check alike: predictive_args, the CSR arrays, the work pointer and n_groups
-static int group_args(const bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                      const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                      int64_t row0, int64_t sample0, const void* work) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || !work || n_groups < 1 || n_groups > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  return BNF_OK;
-}
-
-// *chunk = the sample paths one pass through the work buffer takes, at per_tile bytes per tile and path
-static int group_chunk(int64_t n_rows, int64_t n_samples, size_t per_tile, size_t work_bytes, int64_t* chunk) {
-  const size_t per_sample = (size_t)cdiv(n_rows, kPredTile) * per_tile;
-  *chunk = (int64_t)std::min<size_t>(std::min<size_t>((size_t)n_samples, work_bytes / per_sample), 65535 * 4);
-  if (*chunk < 1)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: one sample path of %lld rows needs %zu", work_bytes,
-                (long long)n_rows, per_sample);
-  return BNF_OK;
-}
-
-static int predictive_group_sums_impl(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                      const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
-                                      int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0, const double* cum,
-                                      void* work, size_t work_bytes, double* out) {
-  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
-                                work)) return rc;
-  if (!out) return fail(BNF_ERR_INVALID, "argument");
-  int64_t chunk;
-  if (const int rc = group_chunk(n_rows, n_samples, 2 * sizeof(double), work_bytes, &chunk)) return rc;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipMemsetAsync(out, 0, (size_t)n_samples * (size_t)n_groups * sizeof(double), h->stream));   // empty groups
-  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
-    const dim3 grid = pred_grid(n_rows, kPredTile, n);
-    double* partial = (double*)work, *o = out + s0 * n_groups;
-    hipLaunchKernelGGL((k_predictive_group_sums<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
-                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
-                       cum, partial, o);
-    hipLaunchKernelGGL(k_predictive_group_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
-                       (int32_t)n_groups, n_rows, n, partial, o);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_predictive_group_sums(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                              const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                              uint64_t seed, int64_t row0, int64_t sample0, void* work, size_t work_bytes, double* out) {
-  return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
-                                    sample0, nullptr, work, work_bytes, out);
-}
-
-// the same paths with member weights: cum_weights DEVICE (n_members,) f64 running sum, NULL = the calls above
-static int no_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BNF_ERR_NO_DEVICE, "no HIP device visible: the BayesNF engine has no CPU fallback (needs gfx950)");
-  return BNF_OK;
-}
-
-int bnf_predictive_samples_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
-                                    const double* cum_weights, float* out) {
-  if (const int rc = no_device()) return rc;
-  return predictive_samples_impl(h, loc, aux, n_members, n_rows, n_samples, seed, row0, sample0, cum_weights, out);
-}
-
-int bnf_predictive_group_sums_weighted(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                       const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
-                                       int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
-                                       const double* cum_weights, void* work, size_t work_bytes, double* out) {
-  if (const int rc = no_device()) return rc;
-  return predictive_group_sums_impl(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, seed, row0,
-                                    sample0, cum_weights, work, work_bytes, out);
-}
-
-// ---- linear combinations of the rows of the sample paths (bnf_combinations.h) ----
-// The position count nnz = form_offsets[n_forms] sizes the grid and the work buffer and lives on the device: it is read
-// back (4 bytes) after everything that can be refused without it has been.
-int bnf_predictive_combinations(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                const int32_t* form_offsets, const int32_t* form_rows, const double* form_coef,
-                                int64_t n_forms, int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
-                                const double* cum_weights, void* work, size_t work_bytes, double* out) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!form_offsets || !form_rows || !form_coef || !work || !out || n_forms < 1 || n_forms > 0x7ffffffeLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  int32_t nnz32 = -1;
-  HIPCHK(hipMemcpyAsync(&nnz32, form_offsets + n_forms, sizeof(nnz32), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  const int64_t nnz = nnz32;
-  if (nnz < 0) return fail(BNF_ERR_INVALID, "form_offsets[n_forms] = %lld: the position count must be in [0, 2^31)", (long long)nnz);
-  int64_t chunk = n_samples;
-  if (nnz > 0)
-    if (const int rc = group_chunk(nnz, n_samples, 2 * sizeof(double), work_bytes, &chunk)) return rc;
-  HIPCHK(hipMemsetAsync(out, 0, (size_t)n_samples * (size_t)n_forms * sizeof(double), h->stream));   // EMPTY forms
-  if (nnz > 0)
-    group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
-      const dim3 grid = pred_grid(nnz, kPredTile, n);
-      double* partial = (double*)work, *o = out + s0 * n_forms;
-      hipLaunchKernelGGL((k_predictive_combinations<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
-                         (int32_t)n_members, n_rows, nnz, form_offsets, form_rows, form_coef, (int32_t)n_forms, n, seed,
-                         row0, sample0 + s0, cum_weights, partial, o);
-      hipLaunchKernelGGL(k_predictive_group_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, form_offsets,
-                         (int32_t)n_forms, nnz, n, partial, o);
-    });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- group peaks and threshold exceedances of the sample paths (bnf_extremes.h) ----
-int bnf_predictive_group_extremes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
-                                  const float* threshold, void* work, size_t work_bytes, double* out_max,
-                                  int32_t* out_argmax, double* out_count, uint32_t* peak_count, uint32_t* exceed_count) {
-  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
-                                work)) return rc;
-  if (!out_max) return fail(BNF_ERR_INVALID, "argument");
-  if ((threshold == nullptr) != (out_count == nullptr) || (exceed_count && !threshold))
-    return fail(BNF_ERR_INVALID, "out_count goes with threshold, and exceed_count needs one");
-  int64_t chunk;
-  if (const int rc = group_chunk(n_rows, n_samples, BNF_EXTREMES_WORK_PER_TILE, work_bytes, &chunk)) return rc;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // groups without a row: max NaN (all bits set), argmax -1, count 0
-  const size_t cells = (size_t)n_samples * (size_t)n_groups;
-  HIPCHK(hipMemsetAsync(out_max, 0xff, cells * sizeof(double), h->stream));
-  if (out_argmax) HIPCHK(hipMemsetAsync(out_argmax, 0xff, cells * sizeof(int32_t), h->stream));
-  if (out_count) HIPCHK(hipMemsetAsync(out_count, 0, cells * sizeof(double), h->stream));
-  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
-    const ExtOut o{seg_rows, out_max + s0 * n_groups, out_argmax ? out_argmax + s0 * n_groups : nullptr,
-                   out_count ? out_count + s0 * n_groups : nullptr, peak_count};
-    const dim3 grid = pred_grid(n_rows, kPredTile, n);
-    hipLaunchKernelGGL((k_predictive_group_extremes<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
-                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
-                       cum_weights, threshold, (ExtPiece*)work, o, exceed_count);
-    hipLaunchKernelGGL(k_predictive_group_extremes_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
-                       (int32_t)n_groups, n_rows, n, (ExtPiece*)work, o);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- spells above a threshold in the sample paths (bnf_episodes.h) ----
-int bnf_predictive_group_episodes(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                  const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                                  uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights,
-                                  const float* threshold, void* work, size_t work_bytes, double* out_longest,
-                                  int32_t* out_longest_row, double* out_spells, double* out_onset_step,
-                                  int32_t* out_first_row, int32_t* out_last_row, uint32_t* onset_count) {
-  if (const int rc = group_args(h, loc, aux, n_members, n_rows, seg_offsets, seg_rows, n_groups, n_samples, row0, sample0,
-                                work)) return rc;
-  if (!threshold || !out_longest) return fail(BNF_ERR_INVALID, "threshold and out_longest are required");
-  int64_t chunk;
-  if (const int rc = group_chunk(n_rows, n_samples, BNF_EPISODES_WORK_PER_TILE, work_bytes, &chunk)) return rc;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // groups without a row: 0 / -1 / 0 / 0 / -1 / -1
-  const size_t cells = (size_t)n_samples * (size_t)n_groups;
-  HIPCHK(hipMemsetAsync(out_longest, 0, cells * sizeof(double), h->stream));
-  if (out_longest_row) HIPCHK(hipMemsetAsync(out_longest_row, 0xff, cells * sizeof(int32_t), h->stream));
-  if (out_spells) HIPCHK(hipMemsetAsync(out_spells, 0, cells * sizeof(double), h->stream));
-  if (out_onset_step) HIPCHK(hipMemsetAsync(out_onset_step, 0, cells * sizeof(double), h->stream));
-  if (out_first_row) HIPCHK(hipMemsetAsync(out_first_row, 0xff, cells * sizeof(int32_t), h->stream));
-  if (out_last_row) HIPCHK(hipMemsetAsync(out_last_row, 0xff, cells * sizeof(int32_t), h->stream));
-  group_passes(h, n_samples, chunk, [&](auto obs, int64_t s0, int64_t n) {
-    const int64_t at = s0 * n_groups;
-    const EpOut o{seg_rows, out_longest + at, out_longest_row ? out_longest_row + at : nullptr,
-                  out_spells ? out_spells + at : nullptr, out_onset_step ? out_onset_step + at : nullptr,
-                  out_first_row ? out_first_row + at : nullptr, out_last_row ? out_last_row + at : nullptr, onset_count};
-    const dim3 grid = pred_grid(n_rows, kPredTile, n);
-    hipLaunchKernelGGL((k_predictive_group_episodes<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
-                       (int32_t)n_members, n_rows, seg_offsets, seg_rows, (int32_t)n_groups, n, seed, row0, sample0 + s0,
-                       cum_weights, threshold, (EpPiece*)work, o);
-    hipLaunchKernelGGL(k_predictive_group_episodes_combine, dim3(grid.x, cdiv(n, 4)), dim3(256), 0, h->stream, seg_offsets,
-                       (int32_t)n_groups, n_rows, n, (EpPiece*)work, o);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- running totals of the sample paths and when they pass a level (bnf_cumulative.h) ----
-// The launch shape of k_predictive_group_cumulative.  Only the block of a tile in which a group STARTS has work, and at
-// most min(tiles, groups) tiles have one; a table that is one long group has a single working tile and is parallel over
-// the samples alone.  So grid.y is pred_grid's 16384 / gx, raised until min(tiles, groups) x grid.y reaches
-// kCumMinBlocks = 2048 blocks (256 CUs x 8), never above the samples.  A block that owns nothing costs one bisection.
-constexpr int64_t kCumMinBlocks = 2048;
-static dim3 cum_grid(int64_t R, int64_t G, int64_t S) {
-  const int64_t gx = cdiv(R, kPredTile);
-  const int64_t want = std::max<int64_t>(std::max<int64_t>(1, 16384 / gx), cdiv(kCumMinBlocks, std::min(gx, G)));
-  return dim3((unsigned)gx, (unsigned)std::min<int64_t>(std::min<int64_t>(S, 65535), want));
-}
-
-int bnf_predictive_group_cumulative(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                    const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups,
-                                    int64_t n_samples, uint64_t seed, int64_t row0, int64_t sample0,
-                                    const double* cum_weights, const double* level, double* out_total,
-                                    double* out_running, double* out_cross_step, int32_t* out_cross_row,
-                                    uint32_t* cross_count, uint32_t* above_count) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  if (!out_total) return fail(BNF_ERR_INVALID, "out_total is required");
-  if (!level && (out_cross_step || out_cross_row || cross_count || above_count))
-    return fail(BNF_ERR_INVALID, "out_cross_step, out_cross_row, cross_count and above_count need a level");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // groups without a row: total 0, cross_step 0 (censored at 0 steps), cross_row -1
-  const size_t cells = (size_t)n_samples * (size_t)n_groups;
-  HIPCHK(hipMemsetAsync(out_total, 0, cells * sizeof(double), h->stream));
-  if (out_cross_step) HIPCHK(hipMemsetAsync(out_cross_step, 0, cells * sizeof(double), h->stream));
-  if (out_cross_row) HIPCHK(hipMemsetAsync(out_cross_row, 0xff, cells * sizeof(int32_t), h->stream));
-  const CumOut o{level, out_total, out_running, out_cross_step, out_cross_row, cross_count, above_count};
-  with_obs(h, [&](auto obs) {
-    hipLaunchKernelGGL((k_predictive_group_cumulative<decltype(obs)::value>), cum_grid(n_rows, n_groups, n_samples),
-                       dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, seg_offsets, seg_rows,
-                       (int32_t)n_groups, n_samples, seed, row0, sample0, cum_weights, o);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- moving-window totals of the sample paths (bnf_windows.h) ----
-// The launch shape is cum_grid's: only the block of a tile in which a group starts has work.
-int bnf_predictive_group_windows(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                                 const int32_t* seg_offsets, const int32_t* seg_rows, int64_t n_groups, int64_t n_samples,
-                                 uint64_t seed, int64_t row0, int64_t sample0, const double* cum_weights, int32_t window,
-                                 const double* threshold, double* out_peak, int32_t* out_peak_row, double* out_window,
-                                 double* out_count, uint32_t* peak_count, uint32_t* exceed_count) {
-  if (const int rc = predictive_args(h, loc, aux, n_members, n_rows, n_samples, row0, sample0)) return rc;
-  if (!seg_offsets || !seg_rows || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  if (!out_peak) return fail(BNF_ERR_INVALID, "out_peak is required");
-  if (window < 1) return fail(BNF_ERR_INVALID, "window must be >= 1 position; got %d", (int)window);
-  if (!threshold && (out_count || exceed_count))
-    return fail(BNF_ERR_INVALID, "out_count and exceed_count need a threshold");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // groups without a candidate window: peak NaN (all bits set), peak_row -1, count 0
-  const size_t cells = (size_t)n_samples * (size_t)n_groups;
-  HIPCHK(hipMemsetAsync(out_peak, 0xff, cells * sizeof(double), h->stream));
-  if (out_peak_row) HIPCHK(hipMemsetAsync(out_peak_row, 0xff, cells * sizeof(int32_t), h->stream));
-  if (out_count) HIPCHK(hipMemsetAsync(out_count, 0, cells * sizeof(double), h->stream));
-  const WinOut o{threshold, out_peak, out_peak_row, out_window, out_count, peak_count, exceed_count};
-  with_obs(h, [&](auto obs) {
-    hipLaunchKernelGGL((k_predictive_group_windows<decltype(obs)::value>), cum_grid(n_rows, n_groups, n_samples),
-                       dim3(256), 0, h->stream, loc, aux, (int32_t)n_members, n_rows, seg_offsets, seg_rows,
-                       (int32_t)n_groups, n_samples, seed, row0, sample0, cum_weights, window, o);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- held-out scoring (bnf_scoring.h) ---------------------------------------------
-static int predictive_scores_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t n_members,
-                                  int64_t n_rows, const float* y, void* work, size_t work_bytes, double* member_ll,
-                                  float* lpd, float* pit, float* crps) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!loc || !aux || !y || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  if (crps && h->cfg.obs_model != BNF_OBS_NORMAL)
-    return fail(BNF_ERR_INVALID, "crps: closed form for the NORMAL observation model only");
-  const int64_t nt = cdiv(n_rows, kScoreTile);
-  const int64_t n_chunks = cdiv(n_members, kScoreChunk);
-  const int64_t n_slots = std::min<int64_t>((n_chunks + 1) / 2, kScoreMaxSlots);
-  const size_t ll_bytes = member_ll ? (size_t)n_members * (size_t)nt * sizeof(double) : 0;
-  const size_t pair_bytes = crps ? (size_t)n_rows * (size_t)n_slots * sizeof(double) : 0;
-  if (ll_bytes + pair_bytes > 0 && (!work || work_bytes < ll_bytes + pair_bytes))
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld members x %lld rows need %zu", work ? work_bytes : (size_t)0,
-                (long long)n_members, (long long)n_rows, ll_bytes + pair_bytes);
-  if (!member_ll && !lpd && !pit && !crps) return BNF_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  double* ll_partial = (double*)work;
-  double* pair_partial = (double*)((char*)work + ll_bytes);
-  with_obs(h, [&](auto obs) {
-    constexpr int OBS = decltype(obs)::value;
-    if (wts)
-      launch_predictive_scores<OBS, true>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots,
-                                          member_ll, lpd, pit, crps);
-    else
-      launch_predictive_scores<OBS, false>(h, loc, aux, wts, n_members, n_rows, y, ll_partial, pair_partial, n_slots,
-                                           member_ll, lpd, pit, crps);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_predictive_scores(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                          const float* y, void* work, size_t work_bytes, double* member_ll, float* lpd, float* pit,
-                          float* crps) {
-  return predictive_scores_impl(h, loc, aux, nullptr, n_members, n_rows, y, work, work_bytes, member_ll, lpd, pit, crps);
-}
-
-// ---- stacking of the members on held-out rows (bnf_stacking.h) ----------------------
-int bnf_member_log_density(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows,
-                           const float* y, float* out) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!loc || !aux || !y || !out || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const dim3 grid(cdiv(n_rows, kStackTile), (unsigned)std::min<int64_t>(n_members, 65535));
-  with_obs(h, [&](auto obs) {
-    hipLaunchKernelGGL((k_member_log_density<decltype(obs)::value>), grid, dim3(256), 0, h->stream, loc, aux,
-                       (int32_t)n_members, n_rows, y, out);
-  });
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_stacking_weights(bnf_handle* h, const float* logdens, int64_t n_members, int64_t n_rows, const double* w_init,
-                         int64_t max_iter, double tol, void* work, size_t work_bytes, double* weights, float* lpd,
-                         double* info) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!logdens || !weights || !info || n_members < 1 || n_members > 0x7fffffffLL || n_rows < 1 || n_rows > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  if (max_iter < 0 || !(tol >= 0.0)) return fail(BNF_ERR_INVALID, "max_iter = %lld, tol = %g: both must be >= 0",
-                                                  (long long)max_iter, tol);
-  const int64_t nt = cdiv(n_rows, kStackTile);
-  const size_t need = sizeof(double) * ((size_t)kStackState + (size_t)(n_members + 3) * (size_t)nt);
-  if (!work || work_bytes < need)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld members x %lld rows need %zu", work ? work_bytes : (size_t)0,
-                (long long)n_members, (long long)n_rows, need);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  double* state = (double*)work;
-  double* tile_stat = state + kStackState;
-  double* partial = tile_stat + 3 * nt;
-  const int32_t M = (int32_t)n_members;
-  hipLaunchKernelGGL(k_stack_init, dim3(1), dim3(256), 0, h->stream, w_init, M, weights, state);
-  // max_iter updates need max_iter + 1 evaluations: the last one is of the weights that are returned
-  bool done = false;
-  for (int64_t left = max_iter + 1; left > 0 && !done;) {
-    const int64_t batch = std::min<int64_t>(left, BNF_STACK_BATCH);
-    for (int64_t i = 0; i < batch; ++i) {
-      hipLaunchKernelGGL((k_stack_rows<false>), dim3((unsigned)nt), dim3(256), 0, h->stream, logdens, M, n_rows,
-                         (const double*)weights, (const double*)state, partial, tile_stat, (float*)nullptr);
-      hipLaunchKernelGGL(k_stack_combine, dim3(1), dim3(256), 0, h->stream, (const double*)partial,
-                         (const double*)tile_stat, M, nt, max_iter, tol, weights, state, info);
-    }
-    left -= batch;
-    HIPCHK(hipGetLastError());
-    double flag = 0.0;
-    HIPCHK(hipMemcpyAsync(&flag, state + STACK_DONE, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    done = flag != 0.0;
-  }
-  if (!done) return fail(BNF_ERR_STATE, "stacking: the iteration budget ran out without the stop being recorded");
-  if (lpd)
-    hipLaunchKernelGGL((k_stack_rows<true>), dim3((unsigned)nt), dim3(256), 0, h->stream, logdens, M, n_rows,
-                       (const double*)weights, (const double*)state, (double*)nullptr, (double*)nullptr, lpd);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
 // ---- held-out validation during a fit (bnf_validation.h) ----------------------------
 int bnf_validation_check(bnf_handle* h, const double* member_ll, int64_t n_scored, int64_t epoch, int32_t check,
                          int32_t n_checks, double* curve, double* best_score, int64_t* best_epoch, int32_t* keep,
@@ -2260,354 +1691,6 @@ int bnf_validation_check(bnf_handle* h, const double* member_ll, int64_t n_score
                      n_checks, M, curve, best_score, best_epoch, keep);
   hipLaunchKernelGGL(k_validation_copy, dim3(cdiv(h->P, kValCopyTile), (unsigned)std::min<int32_t>(M, 65535)), dim3(256), 0,
                      h->stream, (const uint32_t*)h->params, (int64_t)h->P, M, (const int32_t*)keep, (uint32_t*)best_params);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- ranked probability score of count forecasts (bnf_rps.h) -----------------------
-static int count_rps_impl(bnf_handle* h, const float* loc, const float* aux, const double* wts, int64_t n_members,
-                          int64_t n_rows, const float* y, float* rps) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!loc || !aux || !y || !rps || n_members < 1 || n_rows < 1 || n_rows > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  if (n_members > BNF_RPS_MAX_MEMBERS)
-    return fail(BNF_ERR_INVALID, "%lld members: the ranked probability score takes at most %d", (long long)n_members,
-                BNF_RPS_MAX_MEMBERS);
-  if (h->cfg.obs_model == BNF_OBS_NORMAL)
-    return fail(BNF_ERR_INVALID, "rps: count observation models only (NORMAL: the crps of bnf_predictive_scores)");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const bool nb = h->cfg.obs_model == BNF_OBS_NB;
-  if (wts && nb) launch_count_rps<BNF_OBS_NB, true>(h, loc, aux, wts, n_members, n_rows, y, rps);
-  else if (wts) launch_count_rps<BNF_OBS_ZINB, true>(h, loc, aux, wts, n_members, n_rows, y, rps);
-  else if (nb) launch_count_rps<BNF_OBS_NB, false>(h, loc, aux, wts, n_members, n_rows, y, rps);
-  else launch_count_rps<BNF_OBS_ZINB, false>(h, loc, aux, wts, n_members, n_rows, y, rps);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_members, int64_t n_rows, const float* y,
-                  float* rps) {
-  return count_rps_impl(h, loc, aux, nullptr, n_members, n_rows, y, rps);
-}
-
-// ---- the marginal forecast of the WEIGHTED mixture: quantiles, scores and the RPS with member weights ------------------
-// weights DEVICE (n_members,) f64 as bnf_stacking_weights writes them; NULL is BNF_ERR_INVALID (the unweighted calls have
-// their own names).  Not validated: reading them would cost a sync.
-int bnf_normal_mixture_quantiles_weighted(bnf_handle* h, const float* means, const float* scales, const double* weights,
-                                          int64_t n_members, int64_t n_rows, const float* q, int32_t n_q,
-                                          int32_t approximate, float* out) {
-  if (const int rc = no_device()) return rc;
-  if (!weights) return fail(BNF_ERR_INVALID, "weights");
-  return normal_mixture_quantiles_impl(h, means, scales, weights, n_members, n_rows, q, n_q, approximate, out);
-}
-
-int bnf_count_mixture_quantiles_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
-                                         int64_t n_members, int64_t n_rows, const float* q, int32_t n_q, float* means,
-                                         float* out) {
-  if (const int rc = no_device()) return rc;
-  if (!weights) return fail(BNF_ERR_INVALID, "weights");
-  return count_mixture_quantiles_impl(h, loc, aux, weights, n_members, n_rows, q, n_q, means, out);
-}
-
-int bnf_predictive_scores_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights,
-                                   int64_t n_members, int64_t n_rows, const float* y, void* work, size_t work_bytes,
-                                   float* lpd, float* pit, float* crps) {
-  if (const int rc = no_device()) return rc;
-  if (!weights) return fail(BNF_ERR_INVALID, "weights");
-  return predictive_scores_impl(h, loc, aux, weights, n_members, n_rows, y, work, work_bytes, nullptr, lpd, pit, crps);
-}
-
-int bnf_count_rps_weighted(bnf_handle* h, const float* loc, const float* aux, const double* weights, int64_t n_members,
-                           int64_t n_rows, const float* y, float* rps) {
-  if (const int rc = no_device()) return rc;
-  if (!weights) return fail(BNF_ERR_INVALID, "weights");
-  return count_rps_impl(h, loc, aux, weights, n_members, n_rows, y, rps);
-}
-
-// ---- summaries and scores of sample paths (bnf_totals.h) -----------------------------
-static int totals_args(const bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BNF_ERR_NO_DEVICE, "no HIP device visible: the BayesNF engine has no CPU fallback (needs gfx950)");
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!x || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  if (n_samples > BNF_SUMMARY_MAX_SAMPLES)
-    return fail(BNF_ERR_INVALID, "%lld sample paths: a column is sorted in LDS, at most %d", (long long)n_samples,
-                BNF_SUMMARY_MAX_SAMPLES);
-  return BNF_OK;
-}
-
-int bnf_sample_summaries(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
-                         const double* q, int32_t n_q, double* mean, double* quant, double* crps, double* pit) {
-  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
-  if (n_q < 0 || n_q > BNF_SUMMARY_MAX_QUANTILES || (n_q > 0 && (!q || !quant)))
-    return fail(BNF_ERR_INVALID, "n_q = %d: 0..%d quantile levels, with q and quant", n_q, BNF_SUMMARY_MAX_QUANTILES);
-  if (!y && (crps || pit)) return fail(BNF_ERR_INVALID, "crps and pit need the observations y");
-  SummaryQ sq;
-  sq.n = n_q;
-  for (int32_t j = 0; j < kSumMaxQ; ++j) { sq.lo[j] = 0; sq.frac[j] = 0.0; }
-  for (int32_t j = 0; j < n_q; ++j) {
-    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(BNF_ERR_INVALID, "quantile level %g outside [0, 1]", q[j]);
-    const double hq = (double)(n_samples - 1) * q[j];
-    double lo = std::floor(hq);
-    double frac = hq - lo;
-    if (lo >= (double)(n_samples - 1)) { lo = (double)(n_samples - 1); frac = 0.0; }
-    sq.lo[j] = (int32_t)lo;
-    sq.frac[j] = frac;
-  }
-  if (!mean && !crps && !pit && n_q == 0) return BNF_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  launch_sample_summaries(h, x, n_samples, n_cols, y, sq, mean, quant, crps, pit);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_sample_energy_score(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* y,
-                            void* work, size_t work_bytes, double* out) {
-  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
-  if (!y || !out) return fail(BNF_ERR_INVALID, "argument");
-  const size_t need = sizeof(double) * (size_t)energy_work_doubles(n_samples);
-  if (!work || work_bytes < need)
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld sample paths need %zu", work ? work_bytes : (size_t)0,
-                (long long)n_samples, need);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const int64_t nT = energy_tiles(n_samples);
-  hipLaunchKernelGGL(k_energy_first, dim3((unsigned)n_samples), dim3(256), 0, h->stream, x, n_cols, y, (double*)work);
-  hipLaunchKernelGGL(k_energy_pairs, dim3((unsigned)nT, (unsigned)nT), dim3(256), 0, h->stream, x, n_samples, n_cols, y,
-                     (double*)work);
-  hipLaunchKernelGGL(k_energy_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, n_samples,
-                     nT * (nT + 1) / 2, y, n_cols, out);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- covariance, variogram and variogram score of sample paths (bnf_dependence.h) ------
-int bnf_sample_pair_moments(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, double p, const double* y,
-                            const double* pair_w, double* mean, double* cov, double* vario, void* work, size_t work_bytes,
-                            double* score) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!x || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  const int form = p == 0.5 ? 0 : p == 1.0 ? 1 : p == 2.0 ? 2 : -1;
-  if (form < 0) return fail(BNF_ERR_INVALID, "p = %g: the variogram is compiled for p = 0.5, 1 and 2", p);
-  if ((cov || vario || pair_w) && n_cols > BNF_PAIR_MATRIX_MAX_COLS)
-    return fail(BNF_ERR_INVALID, "%lld columns: a pair matrix has at most %d a side", (long long)n_cols,
-                BNF_PAIR_MATRIX_MAX_COLS);
-  const int64_t nT = pair_tiles(n_cols);
-  if (nT > 65535) return fail(BNF_ERR_INVALID, "%lld columns: at most %d pair tiles a side", (long long)n_cols, 65535);
-  if (cov && !mean) return fail(BNF_ERR_INVALID, "cov needs mean: the centred products read it");
-  if (score) {
-    if (!y) return fail(BNF_ERR_INVALID, "score needs the observations y");
-    const size_t need = sizeof(double) * (size_t)pair_work_doubles(n_cols);
-    if (!work || work_bytes < need)
-      return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld columns need %zu", work ? work_bytes : (size_t)0,
-                  (long long)n_cols, need);
-  }
-  if (!mean && !cov && !vario && !score) return BNF_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (mean)
-    hipLaunchKernelGGL(k_column_means, dim3((unsigned)((n_cols + kDpMeanCols - 1) / kDpMeanCols)),
-                       dim3(kDpMeanCols * kDpMeanLanes), 0, h->stream, x, n_samples, n_cols, mean);
-  if (cov || vario || score) {
-    double* partials = score ? (double*)work : nullptr;
-    const double* yy = score ? y : nullptr;
-    const double* ww = score ? pair_w : nullptr;
-    if (!vario && !score)                              // the covariance alone: p plays no part
-      launch_pair_moments<2>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
-    else if (form == 0)
-      launch_pair_moments<0>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
-    else if (form == 1)
-      launch_pair_moments<1>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
-    else
-      launch_pair_moments<2>(h->stream, x, n_samples, n_cols, mean, yy, ww, cov, vario, partials);
-    if (score)
-      hipLaunchKernelGGL(k_vario_finish, dim3(1), dim3(256), 0, h->stream, (const double*)work, nT * (nT + 1) / 2, y,
-                         n_cols, score);
-  }
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- representative scenarios: pairwise distances of the paths, forward selection (bnf_scenarios.h) ------
-static int scenario_sizes(const bnf_handle* h, int64_t n_samples) {
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (n_samples < 1) return fail(BNF_ERR_INVALID, "argument");
-  if (n_samples > BNF_SCENARIO_MAX_SAMPLES)
-    return fail(BNF_ERR_INVALID, "%lld sample paths: the distance matrix has at most %d a side", (long long)n_samples,
-                BNF_SCENARIO_MAX_SAMPLES);
-  return BNF_OK;
-}
-
-int bnf_sample_distances(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
-                         const double* y, int32_t p, double* dist, double* ydist) {
-  if (const int rc = no_device()) return rc;
-  if (const int rc = scenario_sizes(h, n_samples)) return rc;
-  if (!x || !dist || n_cols < 1 || n_cols > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  if (p != 1 && p != 2) return fail(BNF_ERR_INVALID, "p = %d: the distance is the 1-norm (p = 1) or the 2-norm (p = 2)", p);
-  if ((y == nullptr) != (ydist == nullptr))
-    return fail(BNF_ERR_INVALID, "y and ydist go together: both, or both NULL");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (p == 1 && scale) launch_scn_distances<1, true>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
-  else if (p == 1) launch_scn_distances<1, false>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
-  else if (scale) launch_scn_distances<2, true>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
-  else launch_scn_distances<2, false>(h->stream, x, n_samples, n_cols, scale, y, dist, ydist);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_scenario_select(bnf_handle* h, const double* dist, int64_t n_samples, int32_t k, const double* ydist, void* work,
-                        size_t work_bytes, int32_t* chosen, double* objective, double* prob, int32_t* assign,
-                        double* nearest, int32_t* obs_nearest, double* obs) {
-  if (const int rc = no_device()) return rc;
-  if (const int rc = scenario_sizes(h, n_samples)) return rc;
-  if (k < 1 || k > n_samples)
-    return fail(BNF_ERR_INVALID, "k = %d: 1..%lld, the number of sample paths", k, (long long)n_samples);
-  if (!dist || !chosen || !objective || !prob) return fail(BNF_ERR_INVALID, "argument");
-  if (ydist && (!obs_nearest || !obs)) return fail(BNF_ERR_INVALID, "ydist needs obs_nearest and obs");
-  const size_t need = scenario_work_bytes(n_samples);
-  if (!work || work_bytes < need || ((uintptr_t)work & 7u))
-    return fail(BNF_ERR_INVALID, "work buffer of %zu bytes: %lld sample paths need %zu, 8-byte aligned",
-                work ? work_bytes : (size_t)0, (long long)n_samples, need);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const ScnWork w = scenario_work(work, n_samples);
-  const int64_t S = n_samples;
-  HIPCHK(hipMemsetAsync(w.flag, 0, 2 * sizeof(int32_t), h->stream));
-  hipLaunchKernelGGL(k_scn_init, dim3(std::min<unsigned>(1024u, cdiv(S * S, 256 * 4))), dim3(256), 0, h->stream, dist, S, w);
-  for (int32_t i = 0; i < k; ++i) {
-    hipLaunchKernelGGL(k_scn_sums, dim3((unsigned)S), dim3(kScnThreads), 0, h->stream, dist, S, w);
-    hipLaunchKernelGGL(k_scn_pick, dim3(1), dim3(kScnThreads), 0, h->stream, dist, S, i, w, chosen, objective);
-  }
-  hipLaunchKernelGGL(k_scn_assign, dim3(cdiv(S, 256)), dim3(256), 0, h->stream, dist, S, k, w, (const int32_t*)chosen,
-                     assign, nearest);
-  hipLaunchKernelGGL(k_scn_finish, dim3((unsigned)k + 1u), dim3(kScnThreads), 0, h->stream, S, k, w,
-                     (const int32_t*)chosen, ydist, prob, obs_nearest, obs);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- ranks of the columns within a sample path, rank probabilities (bnf_ranking.h) ------
-int bnf_sample_ranks(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const double* scale,
-                     double* out_rank, int32_t* out_above, int32_t* out_ties) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!x || n_samples < 1 || n_cols < 1) return fail(BNF_ERR_INVALID, "argument");
-  if (n_cols > BNF_RANK_MAX_COLS)
-    return fail(BNF_ERR_INVALID, "%lld columns: a path's values are sorted in LDS, at most %d", (long long)n_cols,
-                BNF_RANK_MAX_COLS);
-  if (!out_rank && !out_above && !out_ties) return fail(BNF_ERR_INVALID, "no output: rank, above and ties are all NULL");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  int P = 1;
-  while (P < n_cols) P <<= 1;
-  const int threads = std::min(1024, std::max(64, P / 2));          // a multiple of 64: P is a power of two
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_sample_ranks, (int)(sizeof(uint64_t) * kRankMaxCols), &attr_done);
-  hipLaunchKernelGGL(k_sample_ranks, dim3((unsigned)std::min<int64_t>(n_samples, 1 << 16)), dim3(threads),
-                     sizeof(uint64_t) * (size_t)P, h->stream, x, n_samples, (int32_t)n_cols, (int32_t)P, scale, out_rank,
-                     out_above, out_ties);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_rank_probabilities(bnf_handle* h, const int32_t* above, const int32_t* ties, int64_t n_samples, int64_t n_cols,
-                           int32_t top_k, double* out) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!above || !ties || !out || n_samples < 1 || n_cols < 1 || n_cols > 0x7fffffffLL)
-    return fail(BNF_ERR_INVALID, "argument");
-  if (top_k < 1 || top_k > n_cols)
-    return fail(BNF_ERR_INVALID, "top_k = %d: 1..%lld, the number of columns", top_k, (long long)n_cols);
-  if ((int64_t)top_k * n_cols > BNF_RANK_MAX_CELLS)
-    return fail(BNF_ERR_INVALID, "top_k = %d x %lld columns: at most %d cells", top_k, (long long)n_cols,
-                BNF_RANK_MAX_CELLS);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  hipLaunchKernelGGL(k_rank_probabilities, dim3(cdiv(n_cols, kRankSlab), cdiv(top_k, kRankKPerBlock)), dim3(256), 0,
-                     h->stream, above, ties, n_samples, n_cols, top_k, out);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-// ---- simultaneous bands of sample paths: depths, levels, envelopes (bnf_bands.h) --------
-struct BandSlab { int P, W, threads; };
-static BandSlab band_slab(int64_t S) {
-  BandSlab b;
-  b.P = 1;
-  while (b.P < S) b.P <<= 1;
-  b.W = std::min(kSumMaxCols, kSumMaxSamples / b.P);
-  b.threads = std::min(1024, std::max(64, b.W * b.P / 2));          // a multiple of 64: W * P is a power of two
-  return b;
-}
-
-static int bands_args(const bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
-                      int64_t n_groups) {
-  if (const int rc = totals_args(h, x, n_samples, n_cols)) return rc;
-  if (!col_group || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  return BNF_OK;
-}
-
-int bnf_sample_depths(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
-                      int64_t n_groups, const double* y, int32_t* depth, int32_t* obs_depth) {
-  if (const int rc = bands_args(h, x, n_samples, n_cols, col_group, n_groups)) return rc;
-  if (!depth) return fail(BNF_ERR_INVALID, "depth is NULL");
-  if ((y == nullptr) != (obs_depth == nullptr)) return fail(BNF_ERR_INVALID, "y and obs_depth are given together or not at all");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const BandSlab b = band_slab(n_samples);
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_sample_depths, (int)(sizeof(uint64_t) * kSumMaxSamples), &attr_done);
-  hipLaunchKernelGGL(k_sample_depths, dim3(cdiv(n_cols, b.W)), dim3(b.threads), sizeof(uint64_t) * (size_t)b.W * (size_t)b.P,
-                     h->stream, x, (int32_t)n_samples, n_cols, (int32_t)b.P, (int32_t)b.W, col_group, (int32_t)n_groups, y,
-                     depth, obs_depth);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_depth_levels(bnf_handle* h, const int32_t* depth, int64_t n_samples, int64_t n_groups, const int32_t* need,
-                     int32_t n_cov, const int32_t* k_query, int32_t n_query, const int32_t* obs_depth, int32_t* level,
-                     double* achieved, double* joint, double* obs_pit) {
-  if (const int rc = no_device()) return rc;
-  if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
-  if (!depth || n_samples < 1 || n_groups < 1 || n_groups > 0x7fffffffLL) return fail(BNF_ERR_INVALID, "argument");
-  if (n_samples > BNF_SUMMARY_MAX_SAMPLES)
-    return fail(BNF_ERR_INVALID, "%lld sample paths: the depths are counted in LDS, at most %d", (long long)n_samples,
-                BNF_SUMMARY_MAX_SAMPLES);
-  if (n_cov < 0 || n_cov > BNF_BAND_MAX_LEVELS || (n_cov > 0 && (!need || (!level && !achieved))))
-    return fail(BNF_ERR_INVALID, "n_cov = %d: 0..%d coverage levels, with need and level or achieved", n_cov,
-                BNF_BAND_MAX_LEVELS);
-  if (n_query < 0 || n_query > BNF_BAND_MAX_LEVELS || (n_query > 0 && (!k_query || !joint)))
-    return fail(BNF_ERR_INVALID, "n_query = %d: 0..%d band levels, with k_query and joint", n_query, BNF_BAND_MAX_LEVELS);
-  if (obs_pit && !obs_depth) return fail(BNF_ERR_INVALID, "obs_pit needs obs_depth");
-  if (n_cov < 1 && n_query < 1 && !obs_pit) return fail(BNF_ERR_INVALID, "no output asked for");
-  BandLevels q;
-  q.n_cov = n_cov;
-  q.n_query = n_query;
-  for (int32_t i = 0; i < kBandMaxLevels; ++i) { q.need[i] = 1; q.k_query[i] = 0; }
-  for (int32_t i = 0; i < n_cov; ++i) {
-    if (need[i] < 1 || need[i] > n_samples)
-      return fail(BNF_ERR_INVALID, "need = %d: 1..%lld, the number of sample paths", need[i], (long long)n_samples);
-    q.need[i] = need[i];
-  }
-  for (int32_t i = 0; i < n_query; ++i) q.k_query[i] = k_query[i];
-  HIPCHK(hipSetDevice(h->cfg.device));
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_depth_levels, (int)(sizeof(int32_t) * (kSumMaxSamples + 1)), &attr_done);
-  hipLaunchKernelGGL(k_depth_levels, dim3((unsigned)n_groups), dim3(kBandThreads), sizeof(int32_t) * (size_t)(n_samples + 1),
-                     h->stream, depth, (int32_t)n_samples, (int32_t)n_groups, q, obs_depth, level, achieved, joint, obs_pit);
-  HIPCHK(hipGetLastError());
-  return BNF_OK;
-}
-
-int bnf_sample_envelope(bnf_handle* h, const double* x, int64_t n_samples, int64_t n_cols, const int32_t* col_group,
-                        const int32_t* level, int32_t n_levels, int64_t n_groups, double* lower, double* upper) {
-  if (const int rc = bands_args(h, x, n_samples, n_cols, col_group, n_groups)) return rc;
-  if (!level || !lower || !upper) return fail(BNF_ERR_INVALID, "level, lower or upper is NULL");
-  if (n_levels < 1 || n_levels > BNF_BAND_MAX_LEVELS)
-    return fail(BNF_ERR_INVALID, "n_levels = %d: 1..%d", n_levels, BNF_BAND_MAX_LEVELS);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const BandSlab b = band_slab(n_samples);
-  static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_sample_envelope, (int)(sizeof(uint64_t) * kSumMaxSamples), &attr_done);
-  hipLaunchKernelGGL(k_sample_envelope, dim3(cdiv(n_cols, b.W)), dim3(b.threads),
-                     sizeof(uint64_t) * (size_t)b.W * (size_t)b.P, h->stream, x, (int32_t)n_samples, n_cols, (int32_t)b.P,
-                     (int32_t)b.W, col_group, (int32_t)n_groups, level, n_levels, lower, upper);
   HIPCHK(hipGetLastError());
   return BNF_OK;
 }
@@ -2865,7 +1948,7 @@ int bnf_debug_poison_lds(bnf_handle* h, uint32_t pattern) {
   if (!h || !h->bound) return fail(BNF_ERR_STATE, "not bound");
   HIPCHK(hipSetDevice(h->cfg.device));
   static std::atomic<uint64_t> attr_done{0};
-  allow_lds(h, &k_poison_lds, 160 * 1024, &attr_done);
+  allow_lds(h->cfg.device, &k_poison_lds, 160 * 1024, &attr_done);
   // one workgroup per CU at a time (all of its LDS): several rounds so that every CU is visited
   hipLaunchKernelGGL(k_poison_lds, dim3((unsigned)h->num_cus * 4), dim3(1024), 160 * 1024, h->stream, pattern,
                      (uint32_t*)h->dbg_a);
@@ -2906,183 +1989,6 @@ int bnf_profile_read(bnf_handle* h, int32_t* n, const char** names, double* avg_
   }
   *n = used;
   return BNF_OK;
-}
-
-// ---- posterior gather: RCCL all-gather behind the C ABI (librccl dlopen'ed on first use) ----
-namespace {
-struct RcclId { char internal[BNF_COMM_ID_BYTES]; };   // ncclUniqueId (rccl.h: 128 opaque bytes)
-struct RcclApi {
-  void* lib = nullptr;
-  int (*GetUniqueId)(RcclId*) = nullptr;
-  int (*CommInitRank)(void**, int, RcclId, int) = nullptr;
-  int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-  int (*CommInitAll)(void**, int, const int*) = nullptr;     // one process, several devices (bnf_comm_create_local)
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
-};
-RcclApi g_rccl;
-int rccl_load() {
-  if (g_rccl.lib) return BNF_OK;
-  // Prefer the RCCL the process has ALREADY mapped (a torch host brings its own copy under torch/lib): a second instance
-  // next to it would keep its own bootstrap threads and device state.  /proc/self/maps names it; else the loader's search.
-  void* lib = nullptr;
-  if (FILE* mp = fopen("/proc/self/maps", "r")) {
-    char line[1024];
-    while (!lib && fgets(line, sizeof(line), mp)) {
-      char* pth = strchr(line, '/');
-      if (!pth || !strstr(pth, "librccl.so")) continue;
-      pth[strcspn(pth, "\n")] = 0;
-      lib = dlopen(pth, RTLD_NOW | RTLD_GLOBAL);
-    }
-    fclose(mp);
-  }
-  const char* names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"};
-  for (const char* n : names) {
-    if (lib) break;
-    lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-  }
-  if (!lib) return fail(BNF_ERR_STATE, "cannot dlopen librccl.so: %s", dlerror());
-  g_rccl.GetUniqueId = (int (*)(RcclId*))dlsym(lib, "ncclGetUniqueId");
-  g_rccl.CommInitRank = (int (*)(void**, int, RcclId, int))dlsym(lib, "ncclCommInitRank");
-  g_rccl.AllGather = (int (*)(const void*, void*, size_t, int, void*, hipStream_t))dlsym(lib, "ncclAllGather");
-  g_rccl.CommDestroy = (int (*)(void*))dlsym(lib, "ncclCommDestroy");
-  g_rccl.GetErrorString = (const char* (*)(int))dlsym(lib, "ncclGetErrorString");
-  g_rccl.CommInitAll = (int (*)(void**, int, const int*))dlsym(lib, "ncclCommInitAll");
-  g_rccl.GroupStart = (int (*)())dlsym(lib, "ncclGroupStart");
-  g_rccl.GroupEnd = (int (*)())dlsym(lib, "ncclGroupEnd");
-  // the FULL capability is decided here (bnf_comm_available), so that every rank / caller agrees up front: the
-  // per-rank entry points and the one-process group forms (ncclCommInitAll / ncclGroupStart / ncclGroupEnd)
-  if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllGather || !g_rccl.CommDestroy ||
-      !g_rccl.CommInitAll || !g_rccl.GroupStart || !g_rccl.GroupEnd) {
-    g_rccl = RcclApi{};
-    dlclose(lib);     // (a retry opens it again: do not pile up references)
-    return fail(BNF_ERR_STATE, "librccl.so lacks an expected nccl* symbol");
-  }
-  if (int (*get_version)(int*) = (int (*)(int*))dlsym(lib, "ncclGetVersion")) {   // NCCL API >= 2.7: ncclChar all-gather,
-    int v = 0;                                                                    // group semantics as used here
-    // NCCL_VERSION_CODE is major * 1000 + minor * 100 + patch up to 2.8 and major * 10000 + minor * 100 + patch from 2.9 on
-    // (2.7.8 = 2708, 2.9.6 = 20906): every code below 2700 is older than 2.7 under either encoding
-    if (get_version(&v) == 0 && v > 0 && v < 2700) {
-      g_rccl = RcclApi{};
-      dlclose(lib);
-      return fail(BNF_ERR_STATE, "librccl.so reports NCCL API version %d (< 2.7)", v);
-    }
-  }
-  g_rccl.lib = lib;
-  return BNF_OK;
-}
-int rccl_fail(const char* what, int rc) {
-  return fail(BNF_ERR_HIP, "%s failed: %s", what, g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "rccl error");
-}
-}  // namespace
-
-struct bnf_comm {
-  void* comm = nullptr;
-  int32_t world = 0, rank = 0, device = 0;
-};
-
-int bnf_comm_available(void) {   // local and cheap: dlopen + symbol resolution, no communicator id, no listener thread
-  return rccl_load();
-}
-
-int bnf_comm_unique_id(void* id) {
-  if (!id) return fail(BNF_ERR_INVALID, "null");
-  if (int rc = rccl_load()) return rc;
-  RcclId u;
-  if (int rc = g_rccl.GetUniqueId(&u)) return rccl_fail("ncclGetUniqueId", rc);
-  memcpy(id, u.internal, BNF_COMM_ID_BYTES);
-  return BNF_OK;
-}
-
-int bnf_comm_create(const void* id, int32_t world, int32_t rank, int32_t device, bnf_comm** out) {
-  if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(BNF_ERR_INVALID, "argument");
-  *out = nullptr;
-  if (int rc = rccl_load()) return rc;
-  HIPCHK(hipSetDevice(device));
-  RcclId u;
-  memcpy(u.internal, id, BNF_COMM_ID_BYTES);
-  bnf_comm* c = new bnf_comm();
-  c->world = world; c->rank = rank; c->device = device;
-  if (int rc = g_rccl.CommInitRank(&c->comm, world, u, rank)) {
-    delete c;
-    return rccl_fail("ncclCommInitRank", rc);
-  }
-  *out = c;
-  return BNF_OK;
-}
-
-int bnf_allgather(bnf_comm* c, const void* send, void* recv, size_t bytes_per_rank, void* stream) {
-  if (!c || !send || !recv) return fail(BNF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->device));
-  // ncclChar = 0: byte count is dtype-agnostic
-  if (int rc = g_rccl.AllGather(send, recv, bytes_per_rank, 0, c->comm, (hipStream_t)stream))
-    return rccl_fail("ncclAllGather", rc);
-  return BNF_OK;
-}
-
-// One process driving n devices (the reference's own shape: jax.pmap over jax.local_devices()): one communicator
-// per device from ONE ncclCommInitAll -- no id, no side channel.  RCCL refuses a device listed twice.
-int bnf_comm_create_local(int32_t n, const int32_t* devices, bnf_comm** out) {
-  if (!devices || !out || n < 1 || n > 64) return fail(BNF_ERR_INVALID, "argument");
-  for (int i = 0; i < n; ++i) out[i] = nullptr;
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < i; ++j)
-      if (devices[i] == devices[j]) return fail(BNF_ERR_INVALID, "device %d listed twice: one RCCL rank per device", devices[i]);
-  if (int rc = rccl_load()) return rc;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  std::vector<void*> comms((size_t)n, nullptr);
-  std::vector<int> devs(devices, devices + n);
-  const int rc = g_rccl.CommInitAll(comms.data(), n, devs.data());
-  (void)hipSetDevice(prev);
-  if (rc) return rccl_fail("ncclCommInitAll", rc);
-  for (int i = 0; i < n; ++i) {
-    bnf_comm* c = new bnf_comm();
-    c->comm = comms[(size_t)i]; c->world = n; c->rank = i; c->device = devices[i];
-    out[i] = c;
-  }
-  return BNF_OK;
-}
-
-// The all-gather of every local rank in ONE group call (a single host thread cannot issue them one by one: each
-// would wait for its peers).  send[i] / recv[i] / stream[i] belong to comms[i]'s device.
-int bnf_allgather_group(int32_t n, bnf_comm* const* comms, const void* const* send, void* const* recv,
-                        size_t bytes_per_rank, void* const* streams) {
-  if (!comms || !send || !recv || n < 1) return fail(BNF_ERR_INVALID, "null");
-  for (int i = 0; i < n; ++i) {
-    if (!comms[i] || !send[i] || !recv[i]) return fail(BNF_ERR_INVALID, "null entry %d", i);
-    // the set bnf_comm_create_local made, whole and in order: a partial or permuted set would leave ranks of the
-    // communicator without their call inside the group and ncclGroupEnd waiting for them
-    if (comms[i]->world != n || comms[i]->rank != i)
-      return fail(BNF_ERR_INVALID, "comms[%d] is rank %d of %d: the whole local set in rank order is expected (n = %d)", i,
-                  comms[i]->rank, comms[i]->world, n);
-    // (streams == NULL or streams[i] == NULL: that device's default stream -- a valid hipStream_t, what a torch host
-    // passes for its default current stream)
-  }
-  if (!g_rccl.lib) return fail(BNF_ERR_STATE, "librccl.so not loaded");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (int rc = g_rccl.GroupStart()) return rccl_fail("ncclGroupStart", rc);
-  int first = 0;
-  for (int i = 0; i < n; ++i) {
-    (void)hipSetDevice(comms[i]->device);
-    const int rc = g_rccl.AllGather(send[i], recv[i], bytes_per_rank, 0, comms[i]->comm,
-                                    (hipStream_t)(streams ? streams[i] : nullptr));
-    if (rc && !first) first = rc;
-  }
-  const int rc_end = g_rccl.GroupEnd();
-  (void)hipSetDevice(prev);
-  if (first) return rccl_fail("ncclAllGather (group)", first);
-  if (rc_end) return rccl_fail("ncclGroupEnd", rc_end);
-  return BNF_OK;
-}
-
-void bnf_comm_destroy(bnf_comm* c) {
-  if (!c) return;
-  if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-  delete c;
 }
 
 double bnf_kernel_flops(const bnf_handle* h, const char* name) {

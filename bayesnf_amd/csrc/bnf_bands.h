@@ -42,7 +42,6 @@
 //   has every depth at -1: level -1, achieved 1.  An OD outside [-1, S - 1] gives a NaN obs_pit.
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_ranking.h"
 #include "bnf_totals.h"
 

@@ -27,7 +27,7 @@
 //     found) block-uniformly in LDS from one tile to the next.  Every position is drawn exactly once.  The group's last
 //     piece, of fewer than 1024 positions, is spread over the threads (ceil(left / 256) consecutive positions each): the
 //     few positions by which a short group reaches into the next tile then cost one draw of one wave, not four.
-// The price: a long group is parallel over the sample axis only (the launch sizes grid.y for that, bnf_api.hip cum_grid).
+// The price: a long group is parallel over the sample axis only (the launch sizes grid.y for that, bnf_forecast.hip cum_grid).
 //
 // Order of the f64 additions (it follows the tiling, so it may depend on where a group lies on the position axis, and
 // on nothing else): inside a thread left to right; lanes by the shift-up scan (left operand = the earlier lanes); waves

@@ -36,7 +36,6 @@
 //   finite y_c: NaN.
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_sampling.h"
 #include "bnf_totals.h"
 

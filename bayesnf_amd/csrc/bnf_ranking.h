@@ -31,7 +31,6 @@
 //   not validated: a ties <= 0 gives an empty block (the cell adds nothing), never an access outside the two matrices.
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_totals.h"
 
 namespace bnf {

@@ -55,7 +55,6 @@
 //   columns of a short last chunk are neither written nor read.
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_sampling.h"
 #include "bnf_scoring.h"
 

@@ -45,7 +45,6 @@
 //   With the flag set every kernel writes -1 / NaN instead; the host never waits for the flag.
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_sampling.h"
 #include "bnf_totals.h"
 

@@ -27,7 +27,7 @@
 //   k_score_count_pit                               NB / ZINB: the mixture CDF on either side of y.
 #pragma once
 
-#include "bnf_kernels.h"
+#include "bnf_quantiles.h"
 #include "bnf_sampling.h"
 
 namespace bnf {
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(64) void k_score_rows(const float* __restrict__ loc
   }
 }
 
-// pit of the count models: count_mix_cdf (bnf_kernels.h, f64 for the reason given there) at floor(y) (blockIdx.y = 0) and
+// pit of the count models: count_mix_cdf (bnf_quantiles.h, f64 for the reason given there) at floor(y) (blockIdx.y = 0) and
 // at the largest integer below y (blockIdx.y = 1), 0 below the support.  One lane per (row, side).  `flatten`: left to
 // itself hipcc calls count_mix_cdf as a function, and the call stack is 268 bytes of scratch per lane; inlined there is none.
 template <bool WEIGHTED>

@@ -34,7 +34,6 @@
 //   in a fixed order.  work holds energy_work_doubles(S) doubles (include/bnf.h has the formula).
 #pragma once
 
-#include "bnf_kernels.h"
 #include "bnf_sampling.h"
 
 namespace bnf {

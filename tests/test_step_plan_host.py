@@ -176,12 +176,17 @@ def test_each_switch_set_alone(probe, env, changed):
 
 def test_the_engine_reads_the_environment_in_bnf_create_and_one_debug_call_only():
   """After bnf_create the library calls getenv in exactly one place: BNF_DEBUG_TN_KIND / BNF_DEBUG_TN_SPLITK, arguments
-  of the debug call bnf_debug_gemm_tn."""
-  src = open(os.path.join(ROOT, 'bayesnf_amd', 'csrc', 'bnf_api.hip')).read().split('\n')
-  reads = [l.strip() for l in src if 'getenv' in l and not l.strip().startswith('//')]
+  of the debug call bnf_debug_gemm_tn.  Every unit of the library is read: the three reads are the engine unit's
+  (bnf_api.hip), and the forecast and comm units have none."""
+  csrc = os.path.join(ROOT, 'bayesnf_amd', 'csrc')
+  units = sorted(n for n in os.listdir(csrc) if n.endswith(('.hip', '.cpp')))
+  assert 'bnf_api.hip' in units and len(units) >= 3, units
+  reads = [(name, l.strip()) for name in units for l in open(os.path.join(csrc, name)).read().split('\n')
+           if 'getenv' in l and not l.strip().startswith('//')]
   assert len(reads) == 3, reads
-  assert 'read_switches(getenv)' in reads[0]
-  assert 'BNF_DEBUG_TN_KIND' in reads[1] and 'BNF_DEBUG_TN_SPLITK' in reads[2]
-  for name in os.listdir(os.path.join(ROOT, 'bayesnf_amd', 'csrc')):
+  assert [name for name, _ in reads] == ['bnf_api.hip'] * 3, reads
+  assert 'read_switches(getenv)' in reads[0][1]
+  assert 'BNF_DEBUG_TN_KIND' in reads[1][1] and 'BNF_DEBUG_TN_SPLITK' in reads[2][1]
+  for name in os.listdir(csrc):
     if name.endswith('.h') and name != 'bnf_plan.h':
-      assert 'getenv' not in open(os.path.join(ROOT, 'bayesnf_amd', 'csrc', name)).read(), name
+      assert 'getenv' not in open(os.path.join(csrc, name)).read(), name
