@@ -18,7 +18,8 @@
 //   Each f32 term is converted to double and multiplied by w_m there.  The weights are not validated (reading them would
 //   cost a sync): weights off the simplex give meaningless numbers, never an access outside loc / aux / wts.
 //
-// Arithmetic: every per-(member, row) term is f32; every sum over members, over member pairs and over rows is f64, in an
+// Arithmetic: every per-(member, row) term is f32 (the NORMAL log density: formed in f64 from the f32 difference y - loc
+// and rounded to f32 once); every sum over members, over member pairs and over rows is f64, in an
 // order that depends on the shapes alone (no floating-point atomics): two calls give the same bits.
 //   k_score_member_ll + k_score_member_ll_combine   rows cut into tiles of kScoreTile: fixed tree per (member, tile)
 //     (4 per thread, wave butterfly, 4 waves), then one wave per member adds the tiles (lane = tile mod 64, butterfly).
@@ -45,8 +46,10 @@ static_assert(kScoreTile == 256 * kScoreRowsPerThread, "row tile = one block of 
 template <int OBS>
 __device__ __forceinline__ float score_log_density(float yv, float loc, float a0, float a1, float a2) {
   if constexpr (OBS == BNF_OBS_NORMAL) {
-    const float z = (yv - loc) / a0;
-    return -0.5f * z * z - logf(a0) - 0.918938533204672742f;
+    // f64 from the f32 difference, rounded once: at |z| = 10 the f32 chain (z, z^2, the two subtractions) is off by 1e-5
+    // of a value the rows of member_ll then sum to a few units (sigma = 0.01, members three sigma apart)
+    const double z = (double)(yv - loc) / (double)a0;
+    return (float)(-0.5 * z * z - log((double)a0) - 0.918938533204672742);
   } else {
     const float shape = a1;
     const float tc = 1.0f / shape;

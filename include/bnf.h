@@ -255,7 +255,14 @@ int bnf_forward(bnf_handle* h, const float* theta, int64_t n_members,
  * (n_members,), q HOST (n_q,), out DEVICE (n_q, n_rows).  approximate=0:
  * Chandrupatla root of mean_e Phi((x-mu_e)/sigma_e) - q on
  * [min mu - 5 max sigma, max mu + 5 max sigma], value tolerance 1e-5, <= 60
- * iterations; approximate=1: moment-matched Normal. */
+ * iterations.  Where the f32 grid around the root is coarser than that tolerance
+ * allows (mu = 1e5 with sigma = 0.01: adjacent floats are 0.78 sigma apart) the
+ * iterations run out on a bracket of two adjacent floats and the result is the
+ * one of them with the smaller residual: the root lies within one f32 step of it.
+ * approximate=1: moment-matched Normal, mean + sqrt(var) Phi^-1(q) with
+ * mean = mean_e mu_e first and then var = mean_e (sigma_e^2 + (mu_e - mean)^2),
+ * centred, both f64 with the members in order, the result rounded to f32 (the
+ * one-pass form mean(sigma^2 + mu^2) - mean^2 cancels at the data's own scale). */
 int bnf_normal_mixture_quantiles(bnf_handle* h, const float* means, const float* scales,
                                  int64_t n_members, int64_t n_rows, const float* q,
                                  int32_t n_q, int32_t approximate, float* out);
@@ -577,7 +584,7 @@ int bnf_count_rps(bnf_handle* h, const float* loc, const float* aux, int64_t n_m
  *     pass through without a host trip.  NULL is BNF_ERR_INVALID: the unweighted call has its own name.
  * bnf_normal_mixture_quantiles_weighted: approximate=0 the Chandrupatla root of sum_m w_m Phi((x - mu_m) / sigma_m) - q
  *   (bracket, tolerances and iteration cap of the unweighted call); approximate=1 the moment-matched Normal with
- *   mean = sum w mu, var = sum w (sigma^2 + mu^2) - mean^2.
+ *   mean = sum w mu, then var = sum w (sigma^2 + (mu - mean)^2), centred and f64 as in the unweighted call.
  * bnf_count_mixture_quantiles_weighted: ceil of the root of sum_m w_m cdf_m(x) - q, 0 where sum_m w_m pmf_m(0) > q; the
  *   per-member `means` are unchanged.
  * bnf_predictive_scores_weighted: lpd = log sum_m w_m p_m(y_r) (log space, running max), pit = the weighted mixture CDF at

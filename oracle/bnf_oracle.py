@@ -820,7 +820,9 @@ def normal_quantile_via_root(means, scales, q):
 
 
 def approximate_normal_quantile(means, scales, q):
-  """inference.py:55-84."""
+  """inference.py:55-84.  A restatement of the reference, which forms mean(sd^2 + mu^2) - mean(mu)^2: good for centres of
+  O(1) only -- at mu = 1e5 with sd = 0.01 the difference loses a few per cent of the variance even in float64.  Not a
+  reference beyond that (tests/normal_scale_ref.py `moment_quantile` is: centred)."""
   means = np.asarray(means, dtype=np.float64)
   scales = np.asarray(scales, dtype=np.float64)
   mu = means.reshape(-1, means.shape[-1])

@@ -6,7 +6,7 @@ Two evaluations of the four outputs from the same float32 inputs (loc (M, R), au
                                  (Grimit et al. 2006) summed over ALL ordered pairs -- no use of the symmetry the kernel uses;
   `normal_f32` / `count_f32`     numpy float32, operation by operation, of what the kernels evaluate: every per-(member, row)
                                  term float32, every sum over members, pairs and rows float64 -- the accumulation the kernels
-                                 use.  (The count CDF is float64 on the device too, from a float32 softplus: restated so.)
+                                 use.  (The NORMAL log density is float64 of the float32 difference, rounded once; the count CDF is float64 on the device too, from a float32 softplus: restated so.)
 The GPU tests take their bars from `bar(restatement error)`: max(FP32 gate 1e-5, 4 x the restatement's own error); the
 factor 4 covers the device's expf / logf / erff differing from numpy's by a few ulp.
 
@@ -142,7 +142,8 @@ def normal_f32(loc, sigma, y):
   y0 = np.where(fin, y, F(0))[None, :]
   d = y0 - loc
   z = d / sigma
-  lp = -F(0.5) * z * z - np.log(sigma) - F(0.918938533204672742)
+  z64 = d.astype(np.float64) / sigma.astype(np.float64)      # score_log_density: f64 from the f32 difference, rounded once
+  lp = (-0.5 * z64 * z64 - np.log(sigma.astype(np.float64)) - 0.918938533204672742).astype(F)
   ndtr = F(0.5) * sp.erfc(-(z) * F(0.70710678118654752440))
   first = _abs_moment_f32(d, F(0.70710678118654752440) / sigma, sigma * F(0.79788456080286535588))
   var = (sigma * sigma)[:, 0]

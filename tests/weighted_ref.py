@@ -180,7 +180,8 @@ def normal_f32(loc, sigma, y, w):
   y0 = np.where(fin, y, F(0))[None, :]
   d = y0 - loc
   z = d / sigma
-  lp = -F(0.5) * z * z - np.log(sigma) - F(0.918938533204672742)
+  z64 = d.astype(np.float64) / sigma.astype(np.float64)      # score_log_density: f64 from the f32 difference, rounded once
+  lp = (-0.5 * z64 * z64 - np.log(sigma.astype(np.float64)) - 0.918938533204672742).astype(F)
   ndtr = F(0.5) * sp.erfc(-(z) * F(0.70710678118654752440))
   first = S._abs_moment_f32(d, F(0.70710678118654752440) / sigma, sigma * F(0.79788456080286535588))   # pylint: disable=protected-access
   var = (sigma * sigma)[:, 0]
